@@ -22,6 +22,17 @@ The JSON line also carries
                  achieved = B*H*W * 9216 FLOP/px / duration against the 157.3 TFLOP/s fp32 MFMA peak.
   cpu_baseline : the oracle's C port (oracle/bfcnn_port.c, fp32, OpenMP, all host cores) timed on
                  a bounded sample of the same workload, rank 0 / N=1 only.
+
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit, ms_per_step, dtype, config and the
+roofline (read from HIP events recorded inside the timed steps).  --full adds everything else the default mode measures or
+checks, behind the timed region: parity against the fp64 oracle, the sustained loop, cpu_baseline, the fp32_exact / batch64 /
+compact24 / wide_512 sub-records, short train and unet runs and, with N > 1, the train_dp record.  The other --mode runs do not
+depend on --full.
+
+--dump-outputs DIR (default mode) writes what the last timed step returned to its caller, the denoised uint8 images as float32,
+to DIR/denoised.npy, with the batch indices they are in DIR/denoised_index.npy: the whole batch when it fits in 56 MiB, else a
+fixed seeded sample of images (of image rows, indexed over the B*S rows, when one image alone is larger).  The inputs depend on
+the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -1121,6 +1132,23 @@ def block_roofline(kernel, launches_per_forward, layers, B, S, launch_s, traffic
                 dtype="f32")
 
 
+DUMP_BUDGET_BYTES = 56 << 20        # --dump-outputs stays under 64 MB in all
+
+
+def dump_sample(n_items, item_bytes, seed=0):
+    """indices of the items --dump-outputs writes: all of them when they fit DUMP_BUDGET_BYTES, else a fixed seeded sample"""
+    n = min(n_items, max(1, DUMP_BUDGET_BYTES // item_bytes))
+    if n == n_items:
+        return np.arange(n_items)
+    return np.sort(np.random.default_rng(seed).choice(n_items, n, replace=False))
+
+
+def dump_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def sub_record(model, module, noisy, noisy_host, spec, params, state, O, N, torch, arith, steps, warmup, S, compact=0, check=None):
     """one more timed loop of the default workload on `model` with another arithmetic / batch / activation layout / image size (rank 0,
     N = 1).  check: indices of the images compared with the oracle (default: parity_sample)."""
@@ -1170,8 +1198,13 @@ def main():
     ap.add_argument("--batch", type=int, default=128, help="images per GPU")
     ap.add_argument("--layers", type=int, default=18)
     ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="default mode: after the timed steps also run the parity check, the sustained loop, the CPU baseline, the "
+                         "sub-records and the short train / unet runs (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default mode: write the last timed step's denoised images (float32, a fixed sample when large) to DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sub-records", action="store_true", help="default mode: skip the fp32_exact / batch64 sub-records")
+    ap.add_argument("--no-sub-records", action="store_true", help="default mode with --full: skip the sustained loop and the sub-records")
     ap.add_argument("--unfused", action="store_true", help="one kernel per convolution (A/B only)")
     ap.add_argument("--fused-tile", type=int, default=None, help="exact-fp32 fused-block tile geometry variant (A/B only)")
     ap.add_argument("--arith", type=int, default=1, help="1 = split-f16 fused blocks (default), 0 = exact-fp32 fused blocks")
@@ -1188,6 +1221,10 @@ def main():
                     help="train: BASELINE.json configs[3] -- one data-parallel training step per step (L1 loss, "
                          "batch sharded over the ranks, ONE gradient all-reduce, clip + Adam); not the headline metric")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.mode != "inference":
+        ap.error("--dump-outputs is implemented for the default mode (--mode inference) only")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` by itself: THIS process never touches a GPU (no torch import, no HIP call); it starts
@@ -1289,10 +1326,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs is not None and rank == 0:
+        # what the caller of the last timed step received (uint8 images), before anything else runs on the model
+        # whole images when one fits the budget, else image rows (indices into the B*S rows of the batch)
+        items = out if S * S * int(out.shape[-1]) * 4 <= DUMP_BUDGET_BYTES else out.reshape(B * S, S, -1)
+        sel = dump_sample(items.shape[0], items[0].numel() * 4)
+        got = items[torch.from_numpy(sel).to(out.device)].cpu().numpy()
+        dump_outputs(args.dump_outputs, {"denoised": got.astype(np.float32), "denoised_index": sel.astype(np.float64)})
+
     # a >= 2 s loop of the same step behind the timed region: the package sits at its power cap, so the steady-state rate is a few
     # percent below what a 0.1-0.5 s window shows (profiles/r03_power_probe.txt); every rank runs it, rank 0 reports its own
     sustained = None
-    if not args.no_sub_records:
+    if args.full and not args.no_sub_records:
         n_sus = max(int(2.2 / max(elapsed / args.steps, 1e-4)), args.steps)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -1304,15 +1349,10 @@ def main():
                      "note": "same step, same inputs, run back to back behind the timed region (rank 0's clock, no barrier inside)"}
     # N > 1: the ONE collective of the path -- the data-parallel training step of configs[3] over this run's process group
     train_dp = None
-    if world > 1 and not args.no_sub_records:
+    if world > 1 and args.full and not args.no_sub_records:
         train_dp = train_dp_record(args, torch, bf, O, rank, local_rank, world, dist)
 
     if rank == 0:
-        # parity of the timed configuration: four images spread over the batch against the fp64 oracle (+-1 LSB bar)
-        idx = parity_sample(B)
-        ref = O.denoiser_module_call(spec, params, state, noisy_host[idx])
-        got = out[idx].cpu().numpy()
-        diff = np.abs(got.astype(np.int32) - ref.astype(np.int32))
         images = B * world * args.steps
         value = images / elapsed
         avg_launch_s = block_ms / 1e3 / max(launches, 1)
@@ -1330,10 +1370,16 @@ def main():
                        "blocks": args.layers, "fused_blocks": not args.unfused,
                        "arithmetic": "split-f16 MFMA (f16x3), fp32 accumulate" if h3 else "exact fp32 MFMA",
                        "parallelism": f"replicas x{world}, no collective"},
-            "parity": {"mae_vs_oracle_lsb": float(diff.mean()), "max_abs_lsb": int(diff.max()), "checked_images": len(idx)},
-            "end_to_end_tflops": value / world * gflop_per_image(args.layers, S, S) / 1e3,
-            "roofline": roofline,
         }
+        if args.full:
+            # parity of the timed configuration: four images spread over the batch against the fp64 oracle (+-1 LSB bar)
+            idx = parity_sample(B)
+            ref = O.denoiser_module_call(spec, params, state, noisy_host[idx])
+            got = out[idx].cpu().numpy()
+            diff = np.abs(got.astype(np.int32) - ref.astype(np.int32))
+            result["parity"] = {"mae_vs_oracle_lsb": float(diff.mean()), "max_abs_lsb": int(diff.max()), "checked_images": len(idx)}
+        result["end_to_end_tflops"] = value / world * gflop_per_image(args.layers, S, S) / 1e3
+        result["roofline"] = roofline
         if rehearse:
             result["rehearsal"] = True              # ranks shared a GPU over gloo: exercises the launch path, not a measurement
         if dist is not None:
@@ -1343,9 +1389,9 @@ def main():
             result["sustained"] = sustained
         if train_dp is not None:
             result["train_dp"] = train_dp
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(spec, params, state, noisy_host)
-        if world == 1 and not args.no_sub_records and h3 and args.h3_variant is None:
+        if args.full and world == 1 and not args.no_sub_records and h3 and args.h3_variant is None:
             # the same workload on the other arithmetic / at the north star's batch, timed by this very run (fewer steps):
             #   fp32_exact : --arith 0, exact fp32 on the f32 matrix cores (fused_block_v4_kernel), vs the 157.3 TF fp32 MFMA peak
             #   batch64    : default arithmetic at batch 64 (BASELINE.json north_star: "1x18 resnet 3x3 conv stack at batch 64")
@@ -1370,7 +1416,7 @@ def main():
                 result["wide_512"]["workload"] = f"resnet_color_1x{spec.no_layers}_bn_16x3x3 inference, batch={B // 4} 512x512x3 uint8"
             model.set_option("arith", 1)
             model.set_option("h3_compact", 0)
-        if world == 1 and not args.no_sub_records:
+        if args.full and world == 1 and not args.no_sub_records:
             # BASELINE configs[3] and configs[4] in the driver-run line: short runs of `--mode train` / `--mode unet` (their own
             # roofline, parity against the oracle on a crop, the kernels the library says it launched; CPU legs only in their modes)
             try:

@@ -9,7 +9,7 @@ common = os.environ.get("AB_ARGS", "--steps 10 --warmup 3 --no-cpu-baseline").sp
 rounds = int(os.environ.get("AB_ROUNDS", "2"))
 for r in range(rounds):
     for variant in sys.argv[1:]:
-        out = subprocess.run([sys.executable, "bench.py"] + common + variant.split(), capture_output=True, text=True)
+        out = subprocess.run([sys.executable, "bench.py", "--full"] + common + variant.split(), capture_output=True, text=True)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:
             print(f"[{variant}] FAILED rc={out.returncode}: {out.stderr[-400:]}")

@@ -19,12 +19,12 @@ run_smoke() {
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tee "$out/smoke.log"
 }
 run_bench() {
-    timeout -k 10 600 python bench.py --steps 10 --warmup 3 2> "$out/bench.err" | tee "$out/bench.json"
+    timeout -k 10 600 python bench.py --full --steps 10 --warmup 3 2> "$out/bench.err" | tee "$out/bench.json"
 }
 run_prof() {
     rm -rf "$out/prof"
     cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$out/prof" -- \
-        python "$OLDPWD/bench.py" --steps 5 --warmup 2 --no-cpu-baseline > "$OLDPWD/$out/prof_bench.log" 2>&1
+        python "$OLDPWD/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline > "$OLDPWD/$out/prof_bench.log" 2>&1
     rc=$?
     cd "$OLDPWD"
     find "$out/prof" -name "*kernel_stats.csv" | head -n 1 | xargs -r head -n 25

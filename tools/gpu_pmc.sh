@@ -6,7 +6,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 repo="$PWD"
 cd /tmp
-args="--steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
+args="--full --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
 pass() {
     name="$1"; shift
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$out/$name" -- \

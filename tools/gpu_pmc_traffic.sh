@@ -8,7 +8,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 repo="$PWD"
 cd /tmp
-args="--steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
+args="--full --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
 for c in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$out/$c" -- \
         python "$repo/bench.py" $args > "$out/$c.log" 2>&1 || { echo "pass $c failed"; tail -n 5 "$out/$c.log"; exit 1; }

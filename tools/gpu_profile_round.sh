@@ -18,7 +18,7 @@ rc_all=0
 for m in "${modes[@]}"; do
     a="${ARGS[$m]}"
     echo "== $m: bench"
-    timeout -k 10 400 python bench.py $a --steps 30 --warmup 5 > "$out/${tag}_${m}_bench.json" 2> "$out/${tag}_${m}_bench.err" || { echo "bench $m failed"; tail -n 5 "$out/${tag}_${m}_bench.err"; rc_all=1; continue; }
+    timeout -k 10 400 python bench.py $a --full --steps 30 --warmup 5 > "$out/${tag}_${m}_bench.json" 2> "$out/${tag}_${m}_bench.err" || { echo "bench $m failed"; tail -n 5 "$out/${tag}_${m}_bench.err"; rc_all=1; continue; }
     tail -c 600 "$out/${tag}_${m}_bench.json"; echo
     echo "== $m: rocprofv3 --kernel-trace --stats"
     rm -rf "$out/prof_$m"
