@@ -85,6 +85,7 @@ SIGNATURES = {
     "bf_op_dwconv_ln": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _P]),
     "bf_op_smooth_split": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bf_op_conv2d": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "bf_op_upcat_conv2d": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
     "bf_op_dwconv_mult": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
     "bf_op_bneck_h3_pack_bytes": (C.c_int64, []),
     "bf_op_pack_bneck_h3": (_I, [_P, _P, _P, _P, _P]),

@@ -23,6 +23,10 @@ __device__ __forceinline__ float tp_act_grad(float ref, int act, float alpha, in
             const float c = 0.7071067811865476f, x = ref;
             return 0.5f * (1.f + erff(x * c)) + x * 0.3989422804014327f * expf(-0.5f * x * x);
         }
+        case 4: {                                        // tanh: from its output (the unet's add_clip)
+            const float t = ref_is_output ? ref : tanhf(ref);
+            return 1.f - t * t;
+        }
         default: return 1.f;
     }
 }
@@ -720,7 +724,7 @@ __global__ __launch_bounds__(256) void tp_maxpool2_bwd_kernel(const float* __res
 extern "C" int bf_op_act_bwd(const float* ref, const float* dy, float* dx, int64_t n, int act, float alpha, int ref_is_output, void* stream)
 {
     if (!ref || !dy || !dx || n <= 0) return BF_EINVAL;
-    if (act < 0 || act > 3 || (act == 3 && ref_is_output)) return BF_EUNSUPPORTED;      // GELU is not sign-preserving
+    if (act < 0 || act > 4 || (act == 3 && ref_is_output)) return BF_EUNSUPPORTED;      // GELU is not sign-preserving
     hipLaunchKernelGGL(tp_act_bwd_kernel, dim3(tp_grid(n)), dim3(256), 0, (hipStream_t)stream, ref, dy, dx, n, act, alpha, ref_is_output);
     return TP_OK();
 }

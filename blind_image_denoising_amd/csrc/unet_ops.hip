@@ -351,6 +351,125 @@ extern "C" int bf_op_conv2d(const float* in, float* out, const float* wp, const 
     return hipGetLastError() == hipSuccess ? BF_OK : BF_EHIP;
 }
 
+// ------------------------------------------------------------------------------------------
+// The decoder entry of the plain unet (bfcnn/backbone_blocks.py:383-396): Conv2D k x k, SAME, of
+// Concatenate([UpSampling2D(2, nearest)(up), skip]) without materialising either: up [B,H/2,W/2,C], skip [B,H,W,C],
+// out [B,H,W,C] = res + act(conv(concat) + bias); wp = the 2C -> C kernel packed as for bf_op_conv2d.  Same wave
+// layout and K order as uo_conv2d_kernel (taps outer, 16-channel chunks inner; chunks 0 .. C/16-1 read `up`, the rest
+// `skip`, a wave-uniform switch), so the result is bitwise that of bf_op_conv2d on the materialised concat.
+// ------------------------------------------------------------------------------------------
+template <int C, int NP, int ACT>
+__global__ __launch_bounds__(256, 2) void uo_upcat_conv2d_kernel(const float* __restrict__ up, const float* __restrict__ skip,
+                                                              float* __restrict__ out, const float* __restrict__ wp,
+                                                              const float* __restrict__ res, const float* __restrict__ bias, int B,
+                                                              int H, int W, int k, int pad, float alpha)
+{
+    constexpr int KU = C / 16, KC = 2 * KU, T = C / 16, CIN = 2 * C;
+    const int lane = threadIdx.x & 63, q = lane >> 4, n = lane & 15;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    const int HU = H >> 1, WU = W >> 1;
+    const int64_t npix = (int64_t)B * H * W;
+    const int64_t ngroups = (npix + 16 * NP - 1) / (16 * NP);
+    for (int64_t g = wave; g < ngroups; g += nwaves) {
+        const int64_t p0 = g * 16 * NP;
+        int oy[NP], ox[NP];
+        int64_t ib[NP], ibu[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            int64_t p = p0 + 16 * i + n;
+            p = p < npix ? p : npix - 1;
+            ox[i] = (int)(p % W);
+            oy[i] = (int)((p / W) % H);
+            const int64_t b = p / ((int64_t)W * H);
+            ib[i] = b * H * W;
+            ibu[i] = b * HU * WU;
+        }
+        f32x4 acc[T][NP];
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int i = 0; i < NP; ++i) acc[t][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int tap = 0; tap < k * k; ++tap) {
+            const int ky = tap / k, kx = tap - ky * k;
+            const float* wpo = wp + (int64_t)tap * CIN * C;
+            asm volatile("" : "+s"(wpo));                          // see uo_pointwise_kernel
+            const f32x4* wv = reinterpret_cast<const f32x4*>(wpo) + lane;
+            const float* srcu[NP];
+            const float* srcs[NP];
+            float ok[NP];
+#pragma unroll
+            for (int i = 0; i < NP; ++i) {
+                const int yy = oy[i] + ky - pad, xx = ox[i] + kx - pad;
+                ok[i] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? 1.f : 0.f;
+                const int yc = min(max(yy, 0), H - 1), xc = min(max(xx, 0), W - 1);
+                srcs[i] = skip + (ib[i] + (int64_t)yc * W + xc) * C + 4 * q;
+                srcu[i] = up + (ibu[i] + (int64_t)(yc >> 1) * WU + (xc >> 1)) * C + 4 * q;
+            }
+#pragma unroll
+            for (int c = 0; c < KC; ++c) {
+                f32x4 b[NP];
+#pragma unroll
+                for (int i = 0; i < NP; ++i)
+                    b[i] = *reinterpret_cast<const f32x4*>(c < KU ? srcu[i] + 16 * c : srcs[i] + 16 * (c - KU)) * ok[i];
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    const f32x4 a = wv[(c * T + t) * 64];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int i = 0; i < NP; ++i) acc[t][i] = MFMA4(a[j], b[i][j], acc[t][i]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int64_t p = p0 + 16 * i + n;
+            if (p >= npix) continue;
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                f32x4 v = bf_acc_ready(acc[t][i]);
+                if (bias) v += *reinterpret_cast<const f32x4*>(bias + 16 * t + 4 * q);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = uo_act<ACT>(v[r], alpha);
+                if (res) v += *reinterpret_cast<const f32x4*>(res + p * C + 16 * t + 4 * q);
+                *reinterpret_cast<f32x4*>(out + p * C + 16 * t + 4 * q) = v;
+            }
+        }
+    }
+}
+
+extern "C" int bf_op_upcat_conv2d(const float* up, const float* skip, float* out, const float* wp, const float* res, const float* bias,
+                                  int B, int H, int W, int c_up, int c_skip, int cout, int k, int act, float alpha, void* stream)
+{
+    if (!up || !skip || !out || !wp || B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return BF_EINVAL;
+    if (((uintptr_t)up | (uintptr_t)skip | (uintptr_t)out | (uintptr_t)wp | (uintptr_t)res | (uintptr_t)bias) % 16) return BF_EINVAL;
+    if (act < 0 || act > 3 || (k != 1 && k != 3 && k != 5) || c_up != c_skip || c_up != cout) return BF_EUNSUPPORTED;
+    const int pad = (k - 1) / 2;
+    const int64_t npix = (int64_t)B * H * W;
+    hipStream_t s = (hipStream_t)stream;
+    bool ok = false;
+#define UO_UC_A(CC, NPP, A)                                                                                                    \
+    hipLaunchKernelGGL((uo_upcat_conv2d_kernel<CC, NPP, A>), dim3(uo_grid(npix, 4 * 16 * NPP, 256 * 8)), dim3(256), 0, s, up, skip, out, wp, \
+                       res, bias, B, H, W, k, pad, alpha)
+#define UO_UC(CC, NPP)                                                                                                         \
+    if (cout == CC) {                                                                                                          \
+        ok = true;                                                                                                             \
+        switch (act) {                                                                                                         \
+        case 0: UO_UC_A(CC, NPP, 0); break;                                                                                    \
+        case 1: UO_UC_A(CC, NPP, 1); break;                                                                                    \
+        case 2: UO_UC_A(CC, NPP, 2); break;                                                                                    \
+        default: UO_UC_A(CC, NPP, 3); break;                                                                                   \
+        }                                                                                                                      \
+    }
+    UO_UC(32, 4) UO_UC(64, 4) UO_UC(128, 2)                // NP as bf_op_conv2d's 64 -> 32, 128 -> 64, 256 -> 128 instances
+#undef UO_UC
+#undef UO_UC_A
+    if (!ok) return BF_EUNSUPPORTED;
+    return hipGetLastError() == hipSuccess ? BF_OK : BF_EHIP;
+}
+
 // DepthwiseConv2D k x k with depth_multiplier m (output channel c * m + j, keras order), SAME zero padding, + per-channel
 // bias (a folded BatchNorm shift) + activation: the depthwise middle convolution of the shipped resnet config
 // (backbone_resnet.py:165-176; block_depthwise).  w [k][k][C][m]; thread = 4 consecutive OUTPUT channels of one pixel.

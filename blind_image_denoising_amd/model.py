@@ -59,11 +59,12 @@ def describe_resnet(config: Dict, strict_snapshot: bool = False) -> N.ResnetDesc
     config_backbone = copy.deepcopy(config[BACKBONE_STR])
     config_denoiser = copy.deepcopy(config[DENOISER_STR])
     model_type = config_backbone[TYPE_STR].strip().lower()
-    if model_type in ("unet", "convnext"):
+    if model_type == "convnext":
         raise NotImplementedError(
-            f"backbone [{model_type}] is outside the MI355X hot path (resnet and unet_laplacian only)")
-    if model_type == "unet_laplacian":
-        raise ValueError("unet_laplacian models are described by blind_image_denoising_amd.unet_laplacian")
+            f"backbone [{model_type}] is outside the MI355X hot path (resnet, unet and unet_laplacian only)")
+    if model_type in ("unet", "unet_laplacian"):
+        raise ValueError(f"{model_type} models are described by blind_image_denoising_amd."
+                         f"{'unet_backbone' if model_type == 'unet' else 'unet_laplacian'}")
     if model_type == "efficientnet":
         raise NotImplementedError("efficientnet not implemented yet")          # model.py:213
     if model_type != "resnet":
@@ -479,12 +480,15 @@ class _SubModelView:
 
 
 def _build_hydra(config: Dict, device=None, strict_snapshot: bool = False, seed: Optional[int] = None):
-    """backbone type -> model class: unet_laplacian; the 16-filter 3x3 resnet family (fused engine, trainable); any other
+    """backbone type -> model class: unet_laplacian; unet; the 16-filter 3x3 resnet family (fused engine, trainable); any other
     resnet the operator library covers (per-position kernels / filters, depthwise multipliers, groups; inference)."""
     btype = str(config[BACKBONE_STR].get(TYPE_STR, "")).strip().lower()
     if btype == "unet_laplacian":
         from .unet_laplacian import UnetLaplacianHydra
         return UnetLaplacianHydra(config, device=device, seed=seed)
+    if btype == "unet":
+        from .unet_backbone import UnetHydra
+        return UnetHydra(config, device=device, seed=seed)
     try:
         return HydraModel(config, device=device, strict_snapshot=strict_snapshot, seed=seed)
     except NotImplementedError as first:

@@ -37,6 +37,9 @@ def build_train_functions(model: HydraModel, loss_fn_map: Dict[str, Callable]) -
         return _build_multi_output_train_functions(model, denoiser_loss_fn)
     if type(model).__name__ == "GenericResnetHydra":
         return _build_generic_resnet_train_functions(model, denoiser_loss_fn)
+    if type(model).__name__ == "UnetHydra":
+        from .unet_backbone_train import UnetTrainGraph
+        return _build_generic_resnet_train_functions(model, denoiser_loss_fn, graph_class=UnetTrainGraph)
     state = {"grads": None, "losses": None}
 
     def _buffers():
@@ -77,9 +80,10 @@ def build_train_functions(model: HydraModel, loss_fn_map: Dict[str, Callable]) -
     return TrainFunctions(train_step, test_step, train_step_single_gpu, apply_grads)
 
 
-def _build_generic_resnet_train_functions(model, denoiser_loss_fn, seed: int = 0) -> TrainFunctions:
+def _build_generic_resnet_train_functions(model, denoiser_loss_fn, seed: int = 0, graph_class=None) -> TrainFunctions:
     """the four closures for the resnet configs outside the 16-filter 3x3 engine (GenericResnetHydra), through
-    resnet_generic_train.GenericResnetTrainGraph (explicit forward / backward over the operator library).
+    resnet_generic_train.GenericResnetTrainGraph (explicit forward / backward over the operator library), and for the plain unet
+    (UnetHydra, graph_class = unet_backbone_train.UnetTrainGraph; its blocks are keyed (group, index), model.dropout_blocks()).
     `dropout_rate` (RandomOnOff on every block's branch, backbone_blocks.py:223-225): the per-sample keep factors are drawn here per
     step from a NumPy generator; `train_step_single_gpu.randomness = False` switches them off, `.drop_scale = {block: [B] tensor}`
     pins them (parity tests)."""
@@ -89,7 +93,8 @@ def _build_generic_resnet_train_functions(model, denoiser_loss_fn, seed: int = 0
     d = denoiser_loss_fn.desc(1.0)
     loss_config = {"hinge": d.hinge, "cutoff": d.cutoff, "mae_multiplier": d.mae_multiplier, "mse_multiplier": d.mse_multiplier,
                    "ssim_multiplier": d.ssim_multiplier, "regularization": d.regularization}
-    graph = GenericResnetTrainGraph(model, loss_config)
+    graph = (graph_class or GenericResnetTrainGraph)(model, loss_config)
+    drop_keys = model.dropout_blocks() if hasattr(model, "dropout_blocks") else range(model.no_layers)
     state = {"grads": None}
 
     def train_step(n):
@@ -110,7 +115,7 @@ def _build_generic_resnet_train_functions(model, denoiser_loss_fn, seed: int = 0
         if ds is None and train_step_single_gpu.randomness and rate > 0.0:
             B = int(p_noisy_image_batch.shape[0])
             ds = {i: torch.from_numpy((rng.uniform(size=B) >= rate).astype(np.float32) / np.float32(1.0 - rate)).to(model.device)
-                  for i in range(model.no_layers)}
+                  for i in drop_keys}
         pred, sl, totals = graph.step(p_input_image_batch, p_noisy_image_batch, grads, float(dw), ds)
         model_loss = {REGULARIZATION_LOSS_STR: totals[1], TOTAL_LOSS_STR: totals[2]}
         denoiser_loss = {TOTAL_LOSS_STR: sl[N.BF_LOSS_DENOISER_TOTAL], MSE_LOSS_STR: sl[N.BF_LOSS_MSE], MAE_LOSS_STR: sl[N.BF_LOSS_MAE],

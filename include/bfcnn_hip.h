@@ -229,6 +229,13 @@ int bf_op_pointwise(const float* in, float* out, const float* wp, const float* m
  * upsample_nearest_conv2d (upsampling.py:52-72). */
 int bf_op_conv2d(const float* in, float* out, const float* wp, const float* res, const float* bias, int batch, int height,
                  int width, int cin, int cout, int kh, int kw, int stride, int act, float alpha, void* stream);
+/* The decoder entry of the plain unet (bfcnn/backbone_blocks.py:383-396) in one kernel: out [B,H,W,cout] = res + act(conv_kxk(
+ * Concatenate([UpSampling2D(2, nearest)(up), skip])) + bias), padding="same", stride 1, up [B,H/2,W/2,c_up], skip [B,H,W,c_skip];
+ * neither the upsampled tensor nor the concat is written.  wp = the (c_up + c_skip) -> cout kernel packed as for bf_op_conv2d;
+ * bias / res may be NULL.  Built for c_up = c_skip = cout in {32, 64, 128}, k in {1, 3, 5} (else BF_EUNSUPPORTED); H, W even.
+ * Bitwise equal to bf_upsample2x + bf_op_concat_channels + bf_op_conv2d. */
+int bf_op_upcat_conv2d(const float* up, const float* skip, float* out, const float* wp, const float* res, const float* bias,
+                       int batch, int height, int width, int c_up, int c_skip, int cout, int k, int act, float alpha, void* stream);
 /* DepthwiseConv2D k x k, depth_multiplier m (output channel c*m + j), padding="same", + bias[C*m] (folded BatchNorm shift,
  * may be NULL) + activation (backbone_resnet.py:165-176, block_depthwise); w [k][k][C][m]. */
 int bf_op_dwconv_mult(const float* in, float* out, const float* w, const float* bias, int batch, int height, int width,
@@ -376,7 +383,7 @@ int bf_op_adam_step(float* params, const float* grads, float* m, float* v, int64
  * What `unet_laplacian` training needs beyond the forward operators (bfcnn/train_loop.py:259-312 with the multi-output hydra;
  * tf.GradientTape does this in the reference): exact fp32, NHWC, reductions through caller-supplied scratch (fixed order).
  * act codes as bf_op_pointwise (0 linear, 1 relu, 2 leaky relu(alpha), 3 exact-erf gelu). */
-/* dx = dy * act'(.) ; ref = the activation's input, or (ref_is_output, relu / leaky relu only) its output */
+/* dx = dy * act'(.) ; ref = the activation's input, or (ref_is_output, relu / leaky relu / tanh (4) only) its output */
 int bf_op_act_bwd(const float* ref, const float* dy, float* dx, int64_t n, int act, float alpha, int ref_is_output, void* stream);
 /* 1x1 convolution weight gradient dW[cin][cout] = sum_p x[p][cin] dy[p][cout]; scratch >= cin*cout floats (more = more splits) */
 int bf_op_matmul_wgrad(const float* x, const float* dy, float* dw, int64_t npix, int cin, int cout, float* scratch,
