@@ -281,6 +281,11 @@ def check(rc: int, handle=None, what: str = ""):
     raise RuntimeError(f"HIP error ({rc}) {msg}")
 
 
+def call(fn_name: str, *args):
+    """one C-ABI entry point by name, its status checked"""
+    check(getattr(lib(), fn_name)(*args), None, fn_name)
+
+
 def ptr(t):
     """Device (or host) address of a torch tensor / None."""
     if t is None:

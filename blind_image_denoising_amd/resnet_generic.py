@@ -12,8 +12,7 @@ import torch
 
 from . import _native as N
 from . import unet_laplacian as UL
-
-BN_EPSILON = 1e-3          # DEFAULT_BN_EPSILON (bfcnn/constants.py:9)
+from .op_graph import OpGraphModel, concat_input
 
 
 def channel_gate(x: torch.Tensor, w0: torch.Tensor, w1: torch.Tensor, res: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -148,14 +147,13 @@ def selector_block(x1: torch.Tensor, x2: torch.Tensor, sel: torch.Tensor, w0: to
     return out
 
 
-class GenericResnetHydra:
-    multi_output = False
-    auto_exact_fallback = False
-
-    class _Desc:
-        def __init__(self, cin, cout):
-            self.in_channels, self.out_channels = cin, cout
-            self.denormalize = 1
+class GenericResnetHydra(OpGraphModel):
+    FAMILY = "resnet"
+    # fuse_bottleneck: 1 (default) a block of the shape 1x1 32 -> 32, depthwise 3x3 x4, 1x1 128 -> 32 runs as one kernel with split-f16
+    # GEMMs (bf_op_bneck_block_h3); 0: the fp32 operators (bf_op_pointwise, bf_op_dwmult_pointwise).
+    # arith: 1 (default) the base convolution (k x k, 3 -> 32, k = 3 / 5 / 7) on the f16 matrix cores with split-f16 operands
+    # (bf_op_first_conv_h3k) and the fused bottleneck block where it applies; 0: every product in exact fp32.
+    OPTIONS = ("fuse_bottleneck", "arith")
 
     def __init__(self, config: Dict, device=None, seed: Optional[int] = None):
         bb, dn = config["backbone"], config["denoiser"]
@@ -171,9 +169,7 @@ class GenericResnetHydra:
         self.add_final_bn = bool(bb.get("add_final_bn", False))                        # :274-275
         self.add_channelwise = bool(bb.get("add_channelwise_scaling", False))          # :236-238, 282-283; backbone_blocks.py:215-217
         self.add_multiplier = bool(bb.get("add_learnable_multiplier", False))          # :240-242, 286-287; backbone_blocks.py:219-221
-        self.dropout_rate = float(bb.get("dropout_rate", -1))                          # RandomOnOff (:231-235): identity at inference
-        if self.dropout_rate != -1 and not 0.0 <= self.dropout_rate < 1.0:
-            raise ValueError("dropout_rate must be in [0, 1)")
+        self._parse_dropout(bb)
         if bb.get("base_conv_params") is not None:
             raise NotImplementedError("resnet: base_conv_params is outside the built graph")
         self.selector = None
@@ -194,17 +190,13 @@ class GenericResnetHydra:
             self.selector = dict(scale_type=st, activation_type=at, pool=pool, stride=stride,
                                  compress=max(1, int(round(int(bb.get("filters", 32)) * sp.get("filters_compress_ratio", 0.25)))),
                                  pre=pre if any(pre.values()) else None)
-        if dn.get("use_bias", False) or dn.get("use_bn", False) or dn.get("use_ln", False):
-            raise NotImplementedError("denoiser head: use_bias / use_bn / use_ln are outside the built graph")
+        self._refuse_head_options(dn)
         self.filters = int(bb.get("filters", 32))
         self.kernel_size = int(bb.get("kernel_size", 3))
         self.no_layers = int(bb["no_layers"])
         self.block_kernels = list(bb.get("block_kernels", [3, 3]))
         nb = len(self.block_kernels)
-        if nb <= 0:
-            raise ValueError("len(block_kernels) must be >= 0 ")                     # backbone_resnet.py:110-113
-        if nb > 3:
-            raise ValueError("len(block_kernels) must be <= 3")
+        self._check_block_count(nb)
         self.block_filters = list(bb.get("block_filters", [self.filters] * nb))
         self.block_depthwise = list(bb.get("block_depthwise") or [-1] * nb)
         self.block_groups = list(bb.get("block_groups") or [1] * nb)
@@ -214,16 +206,8 @@ class GenericResnetHydra:
             raise ValueError("len(block_filters) must == len(block_kernels)")         # :116-126
         self.base_activation = bb.get("base_activation", "linear")
         self.block_activation[-1] = self.base_activation                              # :178
-        self.use_bn = bool(bb.get("use_bn", True))
-        self.add_gates = bool(bb.get("add_gates", False))
-        if self.add_gates and nb < 2:
-            raise ValueError("don't know what to do here")                           # backbone_blocks.py:131-141 (gate_no_filters)
-        self.in_channels = int(bb["input_shape"][-1])
-        vr = bb.get("value_range", [0, 255])
-        self.v_min, self.v_max = float(vr[0]), float(vr[1])
-        self.head_filters = int(dn.get("filters", 32))
-        self.head_activation = dn.get("activation", "linear")
-        self.out_channels = int(dn.get("output_channels", 3))
+        self._parse_bn_gates(bb, nb)
+        self._parse_io(bb, dn)
         for a in self.block_activation + [self.base_activation, self.head_activation]:
             UL._act(a)
         # channel bookkeeping + what the operators cover
@@ -240,18 +224,14 @@ class GenericResnetHydra:
             raise ValueError(f"the last block convolution must produce {self.filters} channels for the residual Add (got {cin})")
         if self.head_filters != 32 or self.kernel_size > 7:
             raise NotImplementedError("resnet: head filters must be 32 and the base kernel at most 7x7")
-        self.desc = self._Desc(self.in_channels, self.out_channels)
-        self.device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
-        self._inventory, self._state_inventory = self._build_inventory()
-        self.n_params = sum(int(np.prod(s)) for _, s, _ in self._inventory)
-        self.n_state = sum(int(np.prod(s)) for _, s in self._state_inventory)
-        self.params = torch.from_numpy(self._initial_values(seed)).to(self.device)
-        st = np.concatenate([np.zeros(s, np.float32).ravel() if n.endswith("mean") else np.ones(s, np.float32).ravel()
-                             for n, s in self._state_inventory]) if self._state_inventory else np.zeros(0, np.float32)
-        self.state = torch.from_numpy(st).to(self.device)
-        self.fuse_bottleneck = 1                 # see set_option
+        self._init_storage(device, seed)
+        self.fuse_bottleneck = 1                 # see OPTIONS
         self.arith = 1
-        self._packed = None
+
+    @staticmethod
+    def train_graph_class():
+        from .resnet_generic_train import GenericResnetTrainGraph
+        return GenericResnetTrainGraph
 
     # -- inventory ---------------------------------------------------------------------------
     def _build_inventory(self):
@@ -309,79 +289,13 @@ class GenericResnetHydra:
         out.append(("head/conv1/kernel", (1, 1, self.head_filters, self.out_channels), "conv"))
         return out, state
 
-    @property
-    def trainable_variables(self):
-        o, res = 0, []
-        for name, shape, kind in self._inventory:
-            res.append((name, shape, kind, o))
-            o += int(np.prod(shape))
-        return res
-
-    @property
-    def non_trainable_variables(self):
-        o, res = 0, []
-        for name, shape in self._state_inventory:
-            res.append((name, shape, o))
-            o += int(np.prod(shape))
-        return res
-
-    def count_params(self) -> int:
-        return self.n_params
-
-    def _initial_values(self, seed) -> np.ndarray:
-        from .model import glorot_normal
-        rng = np.random.default_rng(seed)
-        init = lambda s, kind: np.ones(s) if kind == "bn_gamma" else (np.zeros(s) if kind in ("channelwise", "multiplier") else
-            (glorot_normal((1, 1) + tuple(s), rng).reshape(s) if kind == "dense" else glorot_normal(s, rng)))
-        return np.concatenate([np.asarray(init(s, kind), np.float32).ravel() for _, s, kind in self._inventory])
-
-    def get_weights(self):
-        return self.params.detach().cpu().numpy(), self.state.detach().cpu().numpy()
-
-    def set_weights(self, params: np.ndarray, state: Optional[np.ndarray] = None):
-        params = np.ascontiguousarray(params, np.float32).ravel()
-        if params.size != self.n_params:
-            raise ValueError(f"expected {self.n_params} parameters, got {params.size}")
-        self.params.copy_(torch.from_numpy(params))
-        if state is not None:
-            state = np.ascontiguousarray(state, np.float32).ravel()
-            if state.size != self.n_state:
-                raise ValueError(f"expected {self.n_state} state values, got {state.size}")
-            self.state.copy_(torch.from_numpy(state))
-        self.mark_dirty()
-
-    def mark_dirty(self):
-        """parameters or moving statistics changed in place (optimizer / training step): drop the folded operands"""
-        self._packed = None
-        self.version = getattr(self, "version", 0) + 1
-
-    def set_option(self, key: str, value: int):
-        """fuse_bottleneck: 1 (default) a block of the shape 1x1 32 -> 32, depthwise 3x3 x4, 1x1 128 -> 32 runs as one kernel with split-f16
-        GEMMs (bf_op_bneck_block_h3); 0: the fp32 operators (bf_op_pointwise, bf_op_dwmult_pointwise).
-        arith: 1 (default) the base convolution (k x k, 3 -> 32, k = 3 / 5 / 7) on the f16 matrix cores with split-f16 operands
-        (bf_op_first_conv_h3k) and the fused bottleneck block where it applies; 0: every product in exact fp32."""
-        if key not in ("fuse_bottleneck", "arith") or int(value) not in (0, 1):
-            raise ValueError(f"unknown option {key}={value}")
-        setattr(self, key, int(value))
-        self.version = getattr(self, "version", 0) + 1
-
-    def check_status(self, raise_on_overflow: bool = True) -> bool:
-        return True
-
     # -- packing (host arithmetic on the weights only: BatchNorm folding, block-diagonal grouped kernels) ----------------
     def _pack(self):
         if self._packed is not None:
             return self._packed
-        w, st = self.get_weights()
-        W = {n: w[o:o + int(np.prod(s))].reshape(s).astype(np.float64) for n, s, _, o in self.trainable_variables}
-        S = {n: st[o:o + int(np.prod(s))].reshape(s).astype(np.float64) for n, s, o in self.non_trainable_variables}
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device)
+        W, S, dev, bn_affine = self._host_weights()
         P = {"base": dev(W["base/kernel"])}
         homogeneous = lambda a: UL._act(a)[0] in (0, 1, 2)                 # act(s z) = s act(z) for s >= 0: linear, relu, leaky relu
-
-        def bn_affine(base):
-            sc = W[base + "/gamma"] / np.sqrt(S[base + "/moving_variance"] + BN_EPSILON)
-            return sc, -sc * S[base + "/moving_mean"]
 
         def end_scale(prefix, n):
             """relu(w0 + 1) of the ChannelwiseMultiplier times that of the Multiplier behind it: a factor >= 0 per channel"""
@@ -403,9 +317,7 @@ class GenericResnetHydra:
                 cout = cin * dm if dm != -1 else cf
                 scale, shift = np.ones(cout), None
                 if j >= 1 and self.use_bn:              # inference BN folded: y = gamma (x - mean) / sqrt(var + eps), center=False
-                    base = f"block{i}/bn{j}"
-                    scale = W[base + "/gamma"] / np.sqrt(S[base + "/moving_variance"] + BN_EPSILON)
-                    shift = -scale * S[base + "/moving_mean"]
+                    scale, shift = bn_affine(f"block{i}/bn{j}")
                 if j == nb_ - 1 and (self.add_channelwise or self.add_multiplier):
                     # the block's closing multipliers are >= 0 and its last activation is base_activation: folded into the last
                     # convolution's scale / shift when that commutes (and no gate sits between), else applied as their own pass
@@ -465,10 +377,6 @@ class GenericResnetHydra:
         return P
 
     # -- forward -----------------------------------------------------------------------------
-    def _require_gpu(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("resnet inference needs the GPU: there is no CPU execution path")
-
     def _features(self, x: torch.Tensor, H: int, W: int) -> torch.Tensor:
         P = self._pack()
         f = UL.first_conv(x, P["base"], H, W, self.base_activation, True, self.v_min, self.v_max, arith=self.arith)
@@ -519,45 +427,5 @@ class GenericResnetHydra:
         if self.add_final_bn:
             f = UL.dwconv_mult(f, P["final_affine"][0], P["final_affine"][1])
         if self.add_concat_input:
-            B, Hs, Ws, cin = x.shape
-            cat = torch.empty((B, H, W, self._head_cin), dtype=torch.float32, device=f.device)
-            N.check(N.lib().bf_op_concat_input(N.ptr(f), N.ptr(x), int(x.dtype == torch.uint8), N.ptr(cat), B, H, W, Hs, Ws, self.filters, cin,
-                                               self._head_cin, self.v_min, self.v_max, N.stream_ptr(f)), None, "bf_op_concat_input")
-            f = cat
+            f = concat_input(f, x, H, W, self._head_cin, self.v_min, self.v_max)
         return f
-
-    def _as_device(self, x):
-        was_numpy = isinstance(x, np.ndarray)
-        if was_numpy:
-            x = torch.from_numpy(np.ascontiguousarray(x))
-        if x.dim() != 4 or x.shape[-1] != self.in_channels:
-            raise ValueError(f"expected [B,H,W,{self.in_channels}], got {tuple(x.shape)}")
-        if x.dtype != torch.uint8:
-            x = x.to(torch.float32)
-        return x.to(self.device).contiguous(), was_numpy
-
-    def __call__(self, x, training: bool = False):
-        if training:
-            raise NotImplementedError("hydra(x, training=True) on its own is not built here; use train_loop's train_step_single_gpu")
-        self._require_gpu()
-        x, was_numpy = self._as_device(x)
-        B, H, W, _ = x.shape
-        P = self._pack()
-        out = UL.head_fused(self._features(x, H, W), None, P["head0"], self.head_activation, P["head1"], H, W, False, True,
-                            self.v_min, self.v_max, arith=self.arith)
-        if was_numpy:
-            torch.cuda.synchronize(self.device)
-            return out.cpu().numpy()
-        return out
-
-    def predict(self, x):
-        return self(x)
-
-    def infer_u8(self, image: torch.Tensor, cast_to_uint8: bool = True) -> torch.Tensor:
-        from .utilities import next_power_of_2
-        self._require_gpu()
-        B, Hs, Ws, _ = image.shape
-        H, W = next_power_of_2(Hs), next_power_of_2(Ws)
-        P = self._pack()
-        return UL.head_fused(self._features(image, H, W), None, P["head0"], self.head_activation, P["head1"], Hs, Ws, bool(cast_to_uint8), True,
-                             self.v_min, self.v_max, arith=self.arith)

@@ -21,6 +21,7 @@ from .constants import *
 from .custom_logger import logger
 from .loss import loss_function_builder
 from .model import HydraModel, model_builder, save_model
+from .op_graph import OpGraphModel
 from .optimizer import optimizer_builder, deep_supervision_schedule_builder
 from .utilities import load_config
 
@@ -35,11 +36,8 @@ def build_train_functions(model: HydraModel, loss_fn_map: Dict[str, Callable]) -
     denoiser_loss_fn = loss_fn_map[DENOISER_LOSS_FN_STR]
     if getattr(model, "multi_output", False):
         return _build_multi_output_train_functions(model, denoiser_loss_fn)
-    if type(model).__name__ == "GenericResnetHydra":
+    if isinstance(model, OpGraphModel):
         return _build_generic_resnet_train_functions(model, denoiser_loss_fn)
-    if type(model).__name__ == "UnetHydra":
-        from .unet_backbone_train import UnetTrainGraph
-        return _build_generic_resnet_train_functions(model, denoiser_loss_fn, graph_class=UnetTrainGraph)
     state = {"grads": None, "losses": None}
 
     def _buffers():
@@ -80,20 +78,36 @@ def build_train_functions(model: HydraModel, loss_fn_map: Dict[str, Callable]) -
     return TrainFunctions(train_step, test_step, train_step_single_gpu, apply_grads)
 
 
-def _build_generic_resnet_train_functions(model, denoiser_loss_fn, seed: int = 0, graph_class=None) -> TrainFunctions:
-    """the four closures for the resnet configs outside the 16-filter 3x3 engine (GenericResnetHydra), through
-    resnet_generic_train.GenericResnetTrainGraph (explicit forward / backward over the operator library), and for the plain unet
-    (UnetHydra, graph_class = unet_backbone_train.UnetTrainGraph; its blocks are keyed (group, index), model.dropout_blocks()).
+def _loss_config(denoiser_loss_fn) -> Dict:
+    d = denoiser_loss_fn.desc(1.0)
+    return {"hinge": d.hinge, "cutoff": d.cutoff, "mae_multiplier": d.mae_multiplier, "mse_multiplier": d.mse_multiplier,
+            "ssim_multiplier": d.ssim_multiplier, "regularization": d.regularization}
+
+
+def _grad_buffer(model, state: Dict) -> torch.Tensor:
+    """the step's flat gradient (laid out like model.params), allocated once per device"""
+    if state.get("grads") is None or state["grads"].device != model.params.device:
+        state["grads"] = torch.zeros(model.n_params, dtype=torch.float32, device=model.device)
+    return state["grads"]
+
+
+def _loss_dicts(totals, scale_losses):
+    """(model_loss, [denoiser_loss per output]) of the graphs' totals[3] and loss slots"""
+    model_loss = {REGULARIZATION_LOSS_STR: totals[1], TOTAL_LOSS_STR: totals[2]}
+    return model_loss, [{TOTAL_LOSS_STR: sl[N.BF_LOSS_DENOISER_TOTAL], MSE_LOSS_STR: sl[N.BF_LOSS_MSE], MAE_LOSS_STR: sl[N.BF_LOSS_MAE],
+                         SSIM_LOSS_STR: sl[N.BF_LOSS_SSIM]} for sl in scale_losses]
+
+
+def _build_generic_resnet_train_functions(model, denoiser_loss_fn, seed: int = 0) -> TrainFunctions:
+    """the four closures for the single-output operator-graph models -- the resnet configs outside the 16-filter 3x3 engine
+    (GenericResnetHydra) and the plain unet (UnetHydra; its blocks are keyed (group, index), model.dropout_blocks()) -- through the
+    training graph the model names (model.train_graph_class(): explicit forward / backward over the operator library).
     `dropout_rate` (RandomOnOff on every block's branch, backbone_blocks.py:223-225): the per-sample keep factors are drawn here per
     step from a NumPy generator; `train_step_single_gpu.randomness = False` switches them off, `.drop_scale = {block: [B] tensor}`
     pins them (parity tests)."""
     import numpy as np
-    from .resnet_generic_train import GenericResnetTrainGraph
     rng = np.random.default_rng(seed)
-    d = denoiser_loss_fn.desc(1.0)
-    loss_config = {"hinge": d.hinge, "cutoff": d.cutoff, "mae_multiplier": d.mae_multiplier, "mse_multiplier": d.mse_multiplier,
-                   "ssim_multiplier": d.ssim_multiplier, "regularization": d.regularization}
-    graph = (graph_class or GenericResnetTrainGraph)(model, loss_config)
+    graph = model.train_graph_class()(model, _loss_config(denoiser_loss_fn))
     drop_keys = model.dropout_blocks() if hasattr(model, "dropout_blocks") else range(model.no_layers)
     state = {"grads": None}
 
@@ -105,9 +119,7 @@ def _build_generic_resnet_train_functions(model, denoiser_loss_fn, seed: int = 0
 
     def train_step_single_gpu(p_input_image_batch, p_noisy_image_batch, p_depth_weight=(1.0,), p_percentage_done=0.0,
                               p_trainable_variables=None):
-        if state["grads"] is None or state["grads"].device != model.params.device:
-            state["grads"] = torch.zeros(model.n_params, dtype=torch.float32, device=model.device)
-        grads = state["grads"]
+        grads = _grad_buffer(model, state)
         dw = p_depth_weight[0] if hasattr(p_depth_weight, "__len__") else p_depth_weight
         dw = 1.0 if dw is None else dw
         ds = train_step_single_gpu.drop_scale
@@ -117,10 +129,7 @@ def _build_generic_resnet_train_functions(model, denoiser_loss_fn, seed: int = 0
             ds = {i: torch.from_numpy((rng.uniform(size=B) >= rate).astype(np.float32) / np.float32(1.0 - rate)).to(model.device)
                   for i in drop_keys}
         pred, sl, totals = graph.step(p_input_image_batch, p_noisy_image_batch, grads, float(dw), ds)
-        model_loss = {REGULARIZATION_LOSS_STR: totals[1], TOTAL_LOSS_STR: totals[2]}
-        denoiser_loss = {TOTAL_LOSS_STR: sl[N.BF_LOSS_DENOISER_TOTAL], MSE_LOSS_STR: sl[N.BF_LOSS_MSE], MAE_LOSS_STR: sl[N.BF_LOSS_MAE],
-                         SSIM_LOSS_STR: sl[N.BF_LOSS_SSIM]}
-        return totals[0], model_loss, [denoiser_loss], pred, grads
+        return (totals[0],) + _loss_dicts(totals, [sl]) + (pred, grads)
 
     train_step_single_gpu.randomness = True
     train_step_single_gpu.drop_scale = None
@@ -133,17 +142,14 @@ def _build_generic_resnet_train_functions(model, denoiser_loss_fn, seed: int = 0
 
 def _build_multi_output_train_functions(model, denoiser_loss_fn, seed: int = 0) -> TrainFunctions:
     """the same four closures for a multi-output hydra (unet_laplacian): one denoiser loss per output scale against the
-    ground-truth pyramid, times its depth weight (bfcnn/train_loop.py:273-294), through unet_train.UnetTrainGraph.
+    ground-truth pyramid, times its depth weight (bfcnn/train_loop.py:273-294), through model.train_graph_class()
+    (unet_train.UnetTrainGraph).
 
     Training-mode randomness (StochasticDepth on the blocks' branches, dropout on the attention weights:
     backbone_unet_laplacian.py:176-177, 333, 351-352) is drawn here per step from a NumPy generator and handed to the graph as
     explicit scale tensors; `train_step_single_gpu.randomness = False` switches it off (deterministic steps for parity tests)."""
     import numpy as np
-    from .unet_train import UnetTrainGraph
-    d = denoiser_loss_fn.desc(1.0)
-    loss_config = {"hinge": d.hinge, "cutoff": d.cutoff, "mae_multiplier": d.mae_multiplier, "mse_multiplier": d.mse_multiplier,
-                   "ssim_multiplier": d.ssim_multiplier, "regularization": d.regularization}
-    graph = UnetTrainGraph(model, loss_config)
+    graph = model.train_graph_class()(model, _loss_config(denoiser_loss_fn))
     bb = model.config["backbone"]
     depth_drop = [float(r) for r in np.linspace(0.0, max(0.0, float(bb.get("depth_drop_rate", 0.0))), model.width)]
     attn_drop = float(bb.get("convolutional_self_attention_dropout_rate", 0.0))
@@ -179,18 +185,13 @@ def _build_multi_output_train_functions(model, denoiser_loss_fn, seed: int = 0) 
 
     def train_step_single_gpu(p_input_image_batch, p_noisy_image_batch, p_depth_weight=None, p_percentage_done=0.0,
                               p_trainable_variables=None):
-        if state["grads"] is None or state["grads"].device != model.params.device:
-            state["grads"] = torch.zeros(model.n_params, dtype=torch.float32, device=model.device)
-        grads = state["grads"]
+        grads = _grad_buffer(model, state)
         dw = [1.0] * model.depth if p_depth_weight is None else [float(v) for v in p_depth_weight]
         if len(dw) < model.depth:
             raise ValueError(f"{model.depth} output scales need {model.depth} depth weights, got {len(dw)}")
         ds, at = _randomness(*(int(v) for v in p_noisy_image_batch.shape[:3]))
         preds, scale_losses, totals = graph.step(p_input_image_batch, p_noisy_image_batch, dw, grads, ds, at)
-        model_loss = {REGULARIZATION_LOSS_STR: totals[1], TOTAL_LOSS_STR: totals[2]}
-        all_denoiser_loss = [{TOTAL_LOSS_STR: sl[N.BF_LOSS_DENOISER_TOTAL], MSE_LOSS_STR: sl[N.BF_LOSS_MSE], MAE_LOSS_STR: sl[N.BF_LOSS_MAE],
-                              SSIM_LOSS_STR: sl[N.BF_LOSS_SSIM]} for sl in scale_losses]
-        return totals[0], model_loss, all_denoiser_loss, preds, grads
+        return (totals[0],) + _loss_dicts(totals, scale_losses) + (preds, grads)
 
     train_step_single_gpu.randomness = True
 

@@ -20,8 +20,10 @@ import torch
 
 from . import _native as N
 from . import unet_laplacian as UL
+from ._native import call
 from .custom_logger import logger
-from .resnet_generic import BN_EPSILON, channel_gate, scale_add
+from .op_graph import OpGraphModel, concat_input
+from .resnet_generic import channel_gate, scale_add
 
 # channel pairs of the bf_op_conv2d instances (any odd k): the entries, the block convolutions and the unfused decoder entries
 CONV_PAIRS = {(32, 32), (32, 64), (64, 32), (64, 64), (64, 128), (128, 64), (128, 128), (256, 128), (128, 256)}
@@ -44,8 +46,8 @@ def upcat_conv2d(up: torch.Tensor, skip: torch.Tensor, wp: torch.Tensor, cout: i
         raise ValueError(f"upcat_conv2d: up {tuple(up.shape)} is not the half-resolution of skip {tuple(skip.shape)}")
     out = torch.empty((B, H, W, cout), dtype=torch.float32, device=skip.device)
     code, a = UL._act(act)
-    UL._call("bf_op_upcat_conv2d", N.ptr(up), N.ptr(skip), N.ptr(out), N.ptr(wp), N.ptr(res), N.ptr(bias), B, H, W, cu, cs, cout, k,
-             code, a, N.stream_ptr(skip))
+    call("bf_op_upcat_conv2d", N.ptr(up), N.ptr(skip), N.ptr(out), N.ptr(wp), N.ptr(res), N.ptr(bias), B, H, W, cu, cs, cout, k,
+         code, a, N.stream_ptr(skip))
     return out
 
 
@@ -54,9 +56,9 @@ def upsample_concat(up: torch.Tensor, skip: torch.Tensor) -> torch.Tensor:
     B, h, w, cu = up.shape
     cs = skip.shape[-1]
     u = torch.empty((B, 2 * h, 2 * w, cu), dtype=torch.float32, device=up.device)
-    UL._call("bf_upsample2x", N.ptr(up), None, N.ptr(u), B, h, w, cu, 0, 1.0, 0.0, N.stream_ptr(up))
+    call("bf_upsample2x", N.ptr(up), None, N.ptr(u), B, h, w, cu, 0, 1.0, 0.0, N.stream_ptr(up))
     cat = torch.empty((B, 2 * h, 2 * w, cu + cs), dtype=torch.float32, device=up.device)
-    UL._call("bf_op_concat_channels", N.ptr(u), N.ptr(skip), None, N.ptr(cat), B * 4 * h * w, cu, cs, 0, N.stream_ptr(up))
+    call("bf_op_concat_channels", N.ptr(u), N.ptr(skip), None, N.ptr(cat), B * 4 * h * w, cu, cs, 0, N.stream_ptr(up))
     return cat
 
 
@@ -64,18 +66,16 @@ def tanh_(t: torch.Tensor) -> torch.Tensor:
     """tf.tanh (add_clip) as an activation-only pass"""
     out = torch.empty_like(t)
     v = t.view(1, 1, -1, 32)
-    UL._call("bf_op_dwconv_ln", N.ptr(v), N.ptr(out), None, None, 1, 1, v.shape[2], 32, 0, UL.LN_EPSILON, 4, 0.0, N.stream_ptr(t))
+    call("bf_op_dwconv_ln", N.ptr(v), N.ptr(out), None, None, 1, 1, v.shape[2], 32, 0, UL.LN_EPSILON, 4, 0.0, N.stream_ptr(t))
     return out
 
 
-class UnetHydra:
-    multi_output = False
-    auto_exact_fallback = False
-
-    class _Desc:
-        def __init__(self, cin, cout):
-            self.in_channels, self.out_channels = cin, cout
-            self.denormalize = 1
+class UnetHydra(OpGraphModel):
+    FAMILY = "unet"
+    # fuse_upcat: 1 (default) the decoder entries read the upsampled tensor and the skip directly (bf_op_upcat_conv2d);
+    # 0: bf_upsample2x + bf_op_concat_channels + bf_op_conv2d (the same result, bit for bit).
+    OPTIONS = ("fuse_upcat",)
+    arith = 0                           # exact fp32 throughout (not an option here)
 
     def __init__(self, config: Dict, device=None, seed: Optional[int] = None):
         bb, dn = config["backbone"], config["denoiser"]
@@ -102,10 +102,7 @@ class UnetHydra:
         self.block_kernels = [int(k) for k in bb.get("block_kernels", [3, 3])]
         self.block_filters = [int(f) for f in bb.get("block_filters", [32, 32])]
         nb = len(self.block_kernels)
-        if nb <= 0:
-            raise ValueError("len(block_kernels) must be >= 0 ")
-        if nb > 3:
-            raise ValueError("len(block_kernels) must be <= 3")
+        self._check_block_count(nb)
         if len(self.block_filters) <= 0:
             raise ValueError("len(block_filters) must be >= 0 ")
         if nb != len(self.block_filters):
@@ -116,13 +113,8 @@ class UnetHydra:
         self.block_activation = [self.activation] * nb
         self.block_activation[-1] = self.base_activation
         self.entry_activation = self.block_activation[0]
-        self.use_bn = bool(bb.get("use_bn", True))
-        self.add_gates = bool(bb.get("add_gates", False))
-        if self.add_gates and nb < 2:
-            raise ValueError("don't know what to do here")                       # backbone_blocks.py:131-141 (gate_no_filters)
-        self.dropout_rate = float(bb.get("dropout_rate", -1))
-        if self.dropout_rate != -1 and not 0.0 <= self.dropout_rate < 1.0:
-            raise ValueError("dropout_rate must be in [0, 1)")
+        self._parse_bn_gates(bb, nb)
+        self._parse_dropout(bb)
         self.add_multiplier = bool(bb.get("add_learnable_multiplier", False))  # per block (unet_blocks forwards it) and final
         self.add_channelwise = bool(bb.get("add_channelwise_scaling", False))  # final only (unet_blocks drops channelwise_params)
         self.add_initial_bn = bool(bb.get("add_initial_bn", False))            # :216-217
@@ -130,26 +122,17 @@ class UnetHydra:
         self.add_concat_input = bool(bb.get("add_concat_input", False))        # :230-234
         self.add_clip = bool(bb.get("add_clip", False))                        # :254-256
         self.kernel_regularizer = bb.get("kernel_regularizer", "l1")
-        self.in_channels = int(bb["input_shape"][-1])
-        vr = bb.get("value_range", [0, 255])
-        self.v_min, self.v_max = float(vr[0]), float(vr[1])
-        self.head_filters = int(dn.get("filters", 32))
-        self.head_activation = dn.get("activation", "linear")
-        self.out_channels = int(dn.get("output_channels", 3))
+        self._parse_io(bb, dn)
         for a in self.block_activation + [self.activation, self.base_activation, self.head_activation]:
             UL._act(a)
         self._check_channels()
-        self.desc = self._Desc(self.in_channels, self.out_channels)
-        self.device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
-        self._inventory, self._state_inventory = self._build_inventory()
-        self.n_params = sum(int(np.prod(s)) for _, s, _ in self._inventory)
-        self.n_state = sum(int(np.prod(s)) for _, s in self._state_inventory)
-        self.params = torch.from_numpy(self._initial_values(seed)).to(self.device)
-        st = np.concatenate([np.zeros(s, np.float32).ravel() if n.endswith("mean") else np.ones(s, np.float32).ravel()
-                             for n, s in self._state_inventory]) if self._state_inventory else np.zeros(0, np.float32)
-        self.state = torch.from_numpy(st).to(self.device)
-        self.fuse_upcat = 1                     # see set_option
-        self._packed = None
+        self._init_storage(device, seed)
+        self.fuse_upcat = 1                     # see OPTIONS
+
+    @staticmethod
+    def train_graph_class():
+        from .unet_backbone_train import UnetBackboneTrainGraph
+        return UnetBackboneTrainGraph
 
     # -- graph bookkeeping -------------------------------------------------------------------
     def _check_channels(self):
@@ -246,25 +229,6 @@ class UnetHydra:
         out.append(("head/conv1/kernel", (1, 1, self.head_filters, self.out_channels), "conv"))
         return out, state
 
-    @property
-    def trainable_variables(self):
-        o, res = 0, []
-        for name, shape, kind in self._inventory:
-            res.append((name, shape, kind, o))
-            o += int(np.prod(shape))
-        return res
-
-    @property
-    def non_trainable_variables(self):
-        o, res = 0, []
-        for name, shape in self._state_inventory:
-            res.append((name, shape, o))
-            o += int(np.prod(shape))
-        return res
-
-    def count_params(self) -> int:
-        return self.n_params
-
     def block_prefixes(self) -> List[str]:
         """the `no_layers` block groups in graph order: enc0 .. enc{L-1}, dec{L-1} .. dec0"""
         return [f"enc{lv}" for lv in range(self.no_levels)] + [f"dec{lv}" for lv in reversed(range(self.no_levels))]
@@ -273,58 +237,13 @@ class UnetHydra:
         """the keys of RandomOnOff's per-step draw (one per residual block): (group, block index)"""
         return [(pre, i) for pre in self.block_prefixes() for i in range(self.no_layers)]
 
-    def _initial_values(self, seed) -> np.ndarray:
-        from .model import glorot_normal
-        rng = np.random.default_rng(seed)
-        init = lambda s, kind: np.ones(s) if kind == "bn_gamma" else (np.zeros(s) if kind in ("channelwise", "multiplier") else
-            (glorot_normal((1, 1) + tuple(s), rng).reshape(s) if kind == "dense" else glorot_normal(s, rng)))
-        return np.concatenate([np.asarray(init(s, kind), np.float32).ravel() for _, s, kind in self._inventory])
-
-    def get_weights(self):
-        return self.params.detach().cpu().numpy(), self.state.detach().cpu().numpy()
-
-    def set_weights(self, params: np.ndarray, state: Optional[np.ndarray] = None):
-        params = np.ascontiguousarray(params, np.float32).ravel()
-        if params.size != self.n_params:
-            raise ValueError(f"expected {self.n_params} parameters, got {params.size}")
-        self.params.copy_(torch.from_numpy(params))
-        if state is not None:
-            state = np.ascontiguousarray(state, np.float32).ravel()
-            if state.size != self.n_state:
-                raise ValueError(f"expected {self.n_state} state values, got {state.size}")
-            self.state.copy_(torch.from_numpy(state))
-        self.mark_dirty()
-
-    def mark_dirty(self):
-        """parameters or moving statistics changed in place (optimizer / training step): drop the folded operands"""
-        self._packed = None
-        self.version = getattr(self, "version", 0) + 1
-
-    def set_option(self, key: str, value: int):
-        """fuse_upcat: 1 (default) the decoder entries read the upsampled tensor and the skip directly (bf_op_upcat_conv2d);
-        0: bf_upsample2x + bf_op_concat_channels + bf_op_conv2d (the same result, bit for bit)."""
-        if key != "fuse_upcat" or int(value) not in (0, 1):
-            raise ValueError(f"unknown option {key}={value}")
-        setattr(self, key, int(value))
-        self.version = getattr(self, "version", 0) + 1
-
-    def check_status(self, raise_on_overflow: bool = True) -> bool:
-        return True
-
     # -- packing (host arithmetic on the weights only: BatchNorm folding) ------------------------------------------------------
     def _pack(self):
         if self._packed is not None:
             return self._packed
-        w, st = self.get_weights()
-        W = {n: w[o:o + int(np.prod(s))].reshape(s).astype(np.float64) for n, s, _, o in self.trainable_variables}
-        S = {n: st[o:o + int(np.prod(s))].reshape(s).astype(np.float64) for n, s, o in self.non_trainable_variables}
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device)
+        W, S, dev, bn_affine = self._host_weights()
         homogeneous = lambda a: UL._act(a)[0] in (0, 1, 2)                 # act(s z) = s act(z) for s >= 0
         nb = len(self.block_kernels)
-
-        def bn_affine(base):
-            sc = W[base + "/gamma"] / np.sqrt(S[base + "/moving_variance"] + BN_EPSILON)
-            return sc, -sc * S[base + "/moving_mean"]
         P = {"base": dev(W["base/kernel"])}
         if self.add_initial_bn:
             sc, sh = bn_affine("initial_bn")
@@ -374,10 +293,6 @@ class UnetHydra:
         return P
 
     # -- forward -----------------------------------------------------------------------------
-    def _require_gpu(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("unet inference needs the GPU: there is no CPU execution path")
-
     def _blocks(self, f: torch.Tensor, pre: str, P) -> torch.Tensor:
         nb = len(self.block_kernels)
         for i in range(self.no_layers):
@@ -428,52 +343,15 @@ class UnetHydra:
             f = self._blocks(f, f"dec{lv}", P)
         if self.add_final_bn:
             f = UL.dwconv_mult(f, *P["final_bn"])
-        cf = f.shape[-1]
         if self.add_concat_input:
-            B, Hs, Ws, cin = x.shape
-            cat = torch.empty((B, H, W, self._head_cin), dtype=torch.float32, device=f.device)
-            N.check(N.lib().bf_op_concat_input(N.ptr(f), N.ptr(x), int(x.dtype == torch.uint8), N.ptr(cat), B, H, W, Hs, Ws, cf, cin, self._head_cin, self.v_min, self.v_max,
-                                               N.stream_ptr(f)), None, "bf_op_concat_input")
-            f = cat
+            f = concat_input(f, x, H, W, self._head_cin, self.v_min, self.v_max)
         if self.add_clip:
             if "final_scale" in P:
                 f = scale_add(None, f, P["final_scale"])
             f = tanh_(f)
         return f
 
-    def _as_device(self, x):
-        was_numpy = isinstance(x, np.ndarray)
-        if was_numpy:
-            x = torch.from_numpy(np.ascontiguousarray(x))
-        if x.dim() != 4 or x.shape[-1] != self.in_channels:
-            raise ValueError(f"expected [B,H,W,{self.in_channels}], got {tuple(x.shape)}")
-        if x.dtype != torch.uint8:
-            x = x.to(torch.float32)
-        return x.to(self.device).contiguous(), was_numpy
-
     def __call__(self, x, training: bool = False):
-        if training:
-            raise NotImplementedError("hydra(x, training=True) on its own is not built here; use train_loop's train_step_single_gpu")
-        self._check_size(int(x.shape[1]), int(x.shape[2]))
-        self._require_gpu()
-        x, was_numpy = self._as_device(x)
-        B, H, W, _ = x.shape
-        P = self._pack()
-        out = UL.head_fused(self._features(x, H, W), None, P["head0"], self.head_activation, P["head1"], H, W, False, True,
-                            self.v_min, self.v_max, arith=0)
-        if was_numpy:
-            torch.cuda.synchronize(self.device)
-            return out.cpu().numpy()
-        return out
-
-    def predict(self, x):
-        return self(x)
-
-    def infer_u8(self, image: torch.Tensor, cast_to_uint8: bool = True) -> torch.Tensor:
-        from .utilities import next_power_of_2
-        self._require_gpu()
-        B, Hs, Ws, _ = image.shape
-        H, W = next_power_of_2(Hs), next_power_of_2(Ws)
-        P = self._pack()
-        return UL.head_fused(self._features(image, H, W), None, P["head0"], self.head_activation, P["head1"], Hs, Ws, bool(cast_to_uint8),
-                             True, self.v_min, self.v_max, arith=0)
+        if not training:
+            self._check_size(int(x.shape[1]), int(x.shape[2]))
+        return super().__call__(x, training)

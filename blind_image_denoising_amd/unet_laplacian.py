@@ -17,6 +17,8 @@ import numpy as np
 import torch
 
 from . import _native as N
+from ._native import call
+from .op_graph import OpGraphModel
 
 LN_EPSILON = 1e-3          # DEFAULT_LN_EPSILON (bfcnn/constants.py:10); keras LayerNormalization default as well
 ACT_CODES = {"linear": (0, 0.0), "relu": (1, 0.0), "leaky_relu": (2, 0.3), "leakyrelu": (2, 0.3),
@@ -31,10 +33,6 @@ def _act(name: Optional[str]) -> Tuple[int, float]:
     return ACT_CODES[name]
 
 
-def _call(fn_name: str, *args):
-    N.check(getattr(N.lib(), fn_name)(*args), None, fn_name)
-
-
 # ---------------------------------------------------------------------------------------------
 # operator wrappers (float32 NHWC cuda tensors in, new tensor out)
 # ---------------------------------------------------------------------------------------------
@@ -43,7 +41,7 @@ def pack_pointwise(w: torch.Tensor) -> torch.Tensor:
     """[1,1,cin,cout] / [cin,cout] kernel -> matrix-core operand order."""
     cin, cout = w.shape[-2], w.shape[-1]
     out = torch.empty(cin * cout, dtype=torch.float32, device=w.device)
-    _call("bf_op_pack_pointwise", N.ptr(w.contiguous()), N.ptr(out), cin, cout, N.stream_ptr(w))
+    call("bf_op_pack_pointwise", N.ptr(w.contiguous()), N.ptr(out), cin, cout, N.stream_ptr(w))
     return out
 
 
@@ -53,8 +51,8 @@ def pointwise(x: torch.Tensor, wp: torch.Tensor, cout: int, act: str = "linear",
     npix = x.numel() // cin
     out = torch.empty(x.shape[:-1] + (cout,), dtype=torch.float32, device=x.device)
     code, a = _act(act)
-    _call("bf_op_pointwise", N.ptr(x), N.ptr(out), N.ptr(wp), N.ptr(mult), N.ptr(res), npix, cin, cout, code,
-          a if alpha is None else alpha, N.stream_ptr(x))
+    call("bf_op_pointwise", N.ptr(x), N.ptr(out), N.ptr(wp), N.ptr(mult), N.ptr(res), npix, cin, cout, code,
+         a if alpha is None else alpha, N.stream_ptr(x))
     return out
 
 
@@ -64,8 +62,8 @@ def pointwise_ex(x: torch.Tensor, wp: torch.Tensor, cout: int, mode: int, act: s
     cin = x.shape[-1]
     out = torch.empty(x.shape[:-1] + (cout,), dtype=torch.float32, device=x.device)
     code, a = _act(act)
-    _call("bf_op_pointwise_ex", N.ptr(x), N.ptr(out), N.ptr(wp), N.ptr(mult), N.ptr(res), N.ptr(add), x.numel() // cin, cin, cout,
-          code, a, mode, N.stream_ptr(x))
+    call("bf_op_pointwise_ex", N.ptr(x), N.ptr(out), N.ptr(wp), N.ptr(mult), N.ptr(res), N.ptr(add), x.numel() // cin, cin, cout,
+         code, a, mode, N.stream_ptr(x))
     return out
 
 
@@ -74,8 +72,8 @@ def convnext_mlp(x: torch.Tensor, skip: Optional[torch.Tensor], w1p: torch.Tenso
     C = x.shape[-1]
     out = torch.empty_like(x)
     code, a = _act(act)
-    _call("bf_op_convnext_mlp", N.ptr(x), N.ptr(skip), N.ptr(out), N.ptr(w1p), N.ptr(w2p), N.ptr(mult), x.numel() // C, C,
-          code, a, N.stream_ptr(x))
+    call("bf_op_convnext_mlp", N.ptr(x), N.ptr(skip), N.ptr(out), N.ptr(w1p), N.ptr(w2p), N.ptr(mult), x.numel() // C, C,
+         code, a, N.stream_ptr(x))
     return out
 
 
@@ -86,7 +84,7 @@ def pack_mlp_h3(w1: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
     if nbytes < 0:
         raise NotImplementedError(f"split-f16 MLP: C={C} (32 and 64 are built)")
     out = torch.empty(nbytes, dtype=torch.uint8, device=w1.device)
-    _call("bf_op_pack_mlp_h3", N.ptr(w1.contiguous()), N.ptr(w2.contiguous()), N.ptr(out), C, N.stream_ptr(w1))
+    call("bf_op_pack_mlp_h3", N.ptr(w1.contiguous()), N.ptr(w2.contiguous()), N.ptr(out), C, N.stream_ptr(w1))
     return out
 
 
@@ -95,8 +93,8 @@ def convnext_mlp_h3(x: torch.Tensor, skip: Optional[torch.Tensor], packed: torch
     C = x.shape[-1]
     out = torch.empty_like(x)
     code, a = _act(act)
-    _call("bf_op_convnext_mlp_h3", N.ptr(x), N.ptr(skip), N.ptr(out), N.ptr(packed), N.ptr(mult), x.numel() // C, C, code, a,
-          N.stream_ptr(x))
+    call("bf_op_convnext_mlp_h3", N.ptr(x), N.ptr(skip), N.ptr(out), N.ptr(packed), N.ptr(mult), x.numel() // C, C, code, a,
+         N.stream_ptr(x))
     return out
 
 
@@ -106,8 +104,8 @@ def convnext_block1_h3(x: torch.Tensor, dw: torch.Tensor, gamma: Optional[torch.
     C = x.shape[-1]
     out = torch.empty_like(x)
     code, a = _act(act)
-    _call("bf_op_convnext_block1_h3", N.ptr(x), N.ptr(out), N.ptr(dw), N.ptr(gamma), eps, N.ptr(packed), N.ptr(mult),
-          x.numel() // C, C, code, a, N.stream_ptr(x))
+    call("bf_op_convnext_block1_h3", N.ptr(x), N.ptr(out), N.ptr(dw), N.ptr(gamma), eps, N.ptr(packed), N.ptr(mult),
+         x.numel() // C, C, code, a, N.stream_ptr(x))
     return out
 
 
@@ -121,8 +119,8 @@ def convnext_block1_up_h3(enc: torch.Tensor, low: torch.Tensor, dw: torch.Tensor
     out = torch.empty_like(enc)
     code, a = _act(act)
     ucode, ua = _act(act_up)
-    _call("bf_op_convnext_block1_up_h3", N.ptr(enc), N.ptr(low), N.ptr(out), N.ptr(dw), N.ptr(gamma), eps, N.ptr(packed), N.ptr(mult),
-          B, OH, OW, C, code, a, ucode, ua, N.stream_ptr(enc))
+    call("bf_op_convnext_block1_up_h3", N.ptr(enc), N.ptr(low), N.ptr(out), N.ptr(dw), N.ptr(gamma), eps, N.ptr(packed), N.ptr(mult),
+         B, OH, OW, C, code, a, ucode, ua, N.stream_ptr(enc))
     return out
 
 
@@ -131,7 +129,7 @@ def pack_mlp_h3_chain(w1: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
     if int(w1.shape[-2]) != 32:
         raise NotImplementedError("the chain kernel is built for 32 channels")
     out = torch.empty(int(N.lib().bf_op_mlp_h3_pack_bytes(32)), dtype=torch.uint8, device=w1.device)
-    _call("bf_op_pack_mlp_h3_chain", N.ptr(w1.contiguous()), N.ptr(w2.contiguous()), N.ptr(out), 32, N.stream_ptr(w1))
+    call("bf_op_pack_mlp_h3_chain", N.ptr(w1.contiguous()), N.ptr(w2.contiguous()), N.ptr(out), 32, N.stream_ptr(w1))
     return out
 
 
@@ -150,8 +148,8 @@ def convnext_chain32_h3(x: torch.Tensor, low: Optional[torch.Tensor], blocks, ac
     code, a = _act(act)
     ucode, ua = _act(act_up)
     arr = lambda k: (C.c_void_p * n)(*[N.ptr(b[k]) for b in blocks])
-    _call("bf_op_convnext_chain32_h3", N.ptr(x), N.ptr(low), N.ptr(out), n, arr(0), arr(1), arr(2), arr(3), eps, B, OH, OW, code, a,
-          ucode, ua, N.stream_ptr(x))
+    call("bf_op_convnext_chain32_h3", N.ptr(x), N.ptr(low), N.ptr(out), n, arr(0), arr(1), arr(2), arr(3), eps, B, OH, OW, code, a,
+         ucode, ua, N.stream_ptr(x))
     return out
 
 
@@ -161,8 +159,8 @@ def convnext_block_h3(x: torch.Tensor, dw: torch.Tensor, gamma: Optional[torch.T
     B, H, W, C = x.shape
     out = torch.empty_like(x)
     code, a = _act(act)
-    _call("bf_op_convnext_block_h3", N.ptr(x), N.ptr(out), N.ptr(dw), int(dw.shape[0]), N.ptr(gamma), eps, N.ptr(packed),
-          N.ptr(mult), B, H, W, C, code, a, N.stream_ptr(x))
+    call("bf_op_convnext_block_h3", N.ptr(x), N.ptr(out), N.ptr(dw), int(dw.shape[0]), N.ptr(gamma), eps, N.ptr(packed),
+         N.ptr(mult), B, H, W, C, code, a, N.stream_ptr(x))
     return out
 
 
@@ -173,7 +171,7 @@ def dwconv_ln(x: torch.Tensor, w: Optional[torch.Tensor], gamma: Optional[torch.
     k = 0 if w is None else int(w.shape[0])
     out = torch.empty_like(x)
     code, a = _act(act)
-    _call("bf_op_dwconv_ln", N.ptr(x), N.ptr(out), N.ptr(w), N.ptr(gamma), B, H, W, C, k, eps, code, a, N.stream_ptr(x))
+    call("bf_op_dwconv_ln", N.ptr(x), N.ptr(out), N.ptr(w), N.ptr(gamma), B, H, W, C, k, eps, code, a, N.stream_ptr(x))
     return out
 
 
@@ -184,7 +182,7 @@ def smooth_split(x: torch.Tensor, k: int, gauss: Optional[torch.Tensor] = None, 
     lap = torch.empty_like(x)
     down = torch.empty_like(x) if down_stride == 1 else \
         torch.empty((B, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.float32, device=x.device)
-    _call("bf_op_smooth_split", N.ptr(x), N.ptr(lap), N.ptr(down), N.ptr(gauss), B, H, W, C, k, down_stride, N.stream_ptr(x))
+    call("bf_op_smooth_split", N.ptr(x), N.ptr(lap), N.ptr(down), N.ptr(gauss), B, H, W, C, k, down_stride, N.stream_ptr(x))
     return lap, down
 
 
@@ -200,8 +198,8 @@ def conv2d(x: torch.Tensor, wp: torch.Tensor, cout: int, k: int, stride: int = 1
     B, H, W, cin = x.shape
     out = torch.empty((B, -(-H // stride), -(-W // stride), cout), dtype=torch.float32, device=x.device)
     code, a = _act(act)
-    _call("bf_op_conv2d", N.ptr(x), N.ptr(out), N.ptr(wp), N.ptr(res), N.ptr(bias), B, H, W, cin, cout, k, k, stride, code, a,
-          N.stream_ptr(x))
+    call("bf_op_conv2d", N.ptr(x), N.ptr(out), N.ptr(wp), N.ptr(res), N.ptr(bias), B, H, W, cin, cout, k, k, stride, code, a,
+         N.stream_ptr(x))
     return out
 
 
@@ -211,7 +209,7 @@ def dwconv_mult(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], 
     k, m = int(w.shape[0]), int(w.shape[-1])
     out = torch.empty((B, H, W, C * m), dtype=torch.float32, device=x.device)
     code, a = _act(act)
-    _call("bf_op_dwconv_mult", N.ptr(x), N.ptr(out), N.ptr(w), N.ptr(bias), B, H, W, C, m, k, code, a, N.stream_ptr(x))
+    call("bf_op_dwconv_mult", N.ptr(x), N.ptr(out), N.ptr(w), N.ptr(bias), B, H, W, C, m, k, code, a, N.stream_ptr(x))
     return out
 
 
@@ -222,8 +220,8 @@ def dwmult_pointwise(x: torch.Tensor, wd: torch.Tensor, bias1: Optional[torch.Te
     k, m = int(wd.shape[0]), int(wd.shape[-1])
     out = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
     (c1, a1), (c2, a2) = _act(act1), _act(act2)
-    _call("bf_op_dwmult_pointwise", N.ptr(x), N.ptr(out), N.ptr(wd), N.ptr(bias1), c1, a1, N.ptr(wp), N.ptr(bias2), c2, a2,
-          N.ptr(res), B, H, W, C, m, k, cout, N.stream_ptr(x))
+    call("bf_op_dwmult_pointwise", N.ptr(x), N.ptr(out), N.ptr(wd), N.ptr(bias1), c1, a1, N.ptr(wp), N.ptr(bias2), c2, a2,
+         N.ptr(res), B, H, W, C, m, k, cout, N.stream_ptr(x))
     return out
 
 
@@ -232,7 +230,7 @@ def pack_bneck_h3(w0: torch.Tensor, wd: torch.Tensor, w2: torch.Tensor) -> torch
     if tuple(w0.shape) != (32, 32) or tuple(wd.shape) != (3, 3, 32, 4) or tuple(w2.shape) != (128, 32):
         raise ValueError(f"bottleneck operands {tuple(w0.shape)}, {tuple(wd.shape)}, {tuple(w2.shape)}: built for 32 -> 32 -> 3x3 x4 -> 32")
     packed = torch.empty(int(N.lib().bf_op_bneck_h3_pack_bytes()), dtype=torch.uint8, device=w0.device)
-    _call("bf_op_pack_bneck_h3", N.ptr(w0.contiguous()), N.ptr(wd.contiguous()), N.ptr(w2.contiguous()), N.ptr(packed), N.stream_ptr(w0))
+    call("bf_op_pack_bneck_h3", N.ptr(w0.contiguous()), N.ptr(wd.contiguous()), N.ptr(w2.contiguous()), N.ptr(packed), N.stream_ptr(w0))
     return packed
 
 
@@ -242,15 +240,15 @@ def bneck_block_h3(x: torch.Tensor, packed: torch.Tensor, shift0: Optional[torch
     B, H, W, C = x.shape
     out = torch.empty_like(x)
     (c0, a0), (c1, a1), (c2, a2) = _act(act0), _act(act1), _act(act2)
-    _call("bf_op_bneck_block_h3", N.ptr(x), N.ptr(out), N.ptr(packed), N.ptr(shift0), c0, a0, N.ptr(shift1), c1, a1, N.ptr(shift2), c2, a2,
-          int(bool(add_res)), B, H, W, N.stream_ptr(x))
+    call("bf_op_bneck_block_h3", N.ptr(x), N.ptr(out), N.ptr(packed), N.ptr(shift0), c0, a0, N.ptr(shift1), c1, a1, N.ptr(shift2), c2, a2,
+         int(bool(add_res)), B, H, W, N.stream_ptr(x))
     return out
 
 
 def maxpool2(x: torch.Tensor) -> torch.Tensor:
     B, H, W, C = x.shape
     out = torch.empty((B, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.float32, device=x.device)
-    _call("bf_op_maxpool2", N.ptr(x), N.ptr(out), B, H, W, C, N.stream_ptr(x))
+    call("bf_op_maxpool2", N.ptr(x), N.ptr(out), B, H, W, C, N.stream_ptr(x))
     return out
 
 
@@ -261,8 +259,8 @@ def norm_smooth_split(x: torch.Tensor, gamma: Optional[torch.Tensor], act: str, 
     lap = torch.empty_like(x)
     down = torch.empty((B, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.float32, device=x.device)
     code, a = _act(act)
-    _call("bf_op_norm_smooth_split", N.ptr(x), N.ptr(gamma), eps, code, a, N.ptr(gauss), N.ptr(lap), N.ptr(down), B, H, W, C, k,
-          N.stream_ptr(x))
+    call("bf_op_norm_smooth_split", N.ptr(x), N.ptr(gamma), eps, code, a, N.ptr(gauss), N.ptr(lap), N.ptr(down), B, H, W, C, k,
+         N.stream_ptr(x))
     return lap, down
 
 
@@ -270,7 +268,7 @@ def upsample_act_add(x: torch.Tensor, other: Optional[torch.Tensor], act: str = 
     B, H, W, C = x.shape
     out = torch.empty((B, 2 * H, 2 * W, C), dtype=torch.float32, device=x.device)
     code, a = _act(act)
-    _call("bf_op_upsample_act_add", N.ptr(x), N.ptr(other), N.ptr(out), B, H, W, C, code, a, N.stream_ptr(x))
+    call("bf_op_upsample_act_add", N.ptr(x), N.ptr(other), N.ptr(out), B, H, W, C, code, a, N.stream_ptr(x))
     return out
 
 
@@ -283,21 +281,21 @@ def conv2d_transpose(x: torch.Tensor, w: torch.Tensor, stride: int = 2, act: str
         raise ValueError(f"kernel {tuple(w.shape)} does not fit {cin} input channels")
     out = torch.empty((B, H * stride, W * stride, cout), dtype=torch.float32, device=x.device)
     code, a = _act(act)
-    _call("bf_op_conv2d_transpose", N.ptr(x), N.ptr(w), N.ptr(out), B, H, W, cin, cout, k, int(stride), code, a, N.stream_ptr(x))
+    call("bf_op_conv2d_transpose", N.ptr(x), N.ptr(w), N.ptr(out), B, H, W, cin, cout, k, int(stride), code, a, N.stream_ptr(x))
     return out
 
 
 def resize_bilinear(x: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
     B, H, W, C = x.shape
     out = torch.empty((B, oh, ow, C), dtype=torch.float32, device=x.device)
-    _call("bf_op_resize_bilinear", N.ptr(x), N.ptr(out), B, H, W, C, oh, ow, N.stream_ptr(x))
+    call("bf_op_resize_bilinear", N.ptr(x), N.ptr(out), B, H, W, C, oh, ow, N.stream_ptr(x))
     return out
 
 
 def attention(q: torch.Tensor, v: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
     B, T, A = q.shape
     out = torch.empty_like(q)
-    _call("bf_op_attention", N.ptr(q), N.ptr(v), N.ptr(k), N.ptr(out), B, T, A, N.stream_ptr(q))
+    call("bf_op_attention", N.ptr(q), N.ptr(v), N.ptr(k), N.ptr(out), B, T, A, N.stream_ptr(q))
     return out
 
 
@@ -308,7 +306,7 @@ def attention_interleaved(qvk: torch.Tensor, A: int) -> torch.Tensor:
     if not qvk.is_contiguous():
         raise ValueError("tensor must be contiguous")
     at = lambda floats: N.C.c_void_p(qvk.data_ptr() + 4 * floats)
-    _call("bf_op_attention_ld", at(0), at(A), at(2 * A), N.ptr(out), B, T, A, ld, N.stream_ptr(qvk))
+    call("bf_op_attention_ld", at(0), at(A), at(2 * A), N.ptr(out), B, T, A, ld, N.stream_ptr(qvk))
     return out
 
 
@@ -321,11 +319,11 @@ def first_conv(x: torch.Tensor, w: torch.Tensor, H: int, W: int, act: str, norma
     out = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
     code, a = _act(act)
     if arith == 1 and k in (3, 5, 7) and (cin, cout) == (3, 32):
-        _call("bf_op_first_conv_h3k", N.ptr(x), int(x.dtype == torch.uint8), N.ptr(out), N.ptr(w), B, Hs, Ws, H, W, k, int(normalize),
-              v_min, v_max, code, a, N.stream_ptr(x))
+        call("bf_op_first_conv_h3k", N.ptr(x), int(x.dtype == torch.uint8), N.ptr(out), N.ptr(w), B, Hs, Ws, H, W, k, int(normalize),
+             v_min, v_max, code, a, N.stream_ptr(x))
         return out
-    _call("bf_op_first_conv", N.ptr(x), int(x.dtype == torch.uint8), N.ptr(out), N.ptr(w), B, Hs, Ws, H, W, cin, cout, k,
-          int(normalize), v_min, v_max, code, a, N.stream_ptr(x))
+    call("bf_op_first_conv", N.ptr(x), int(x.dtype == torch.uint8), N.ptr(out), N.ptr(w), B, Hs, Ws, H, W, cin, cout, k,
+         int(normalize), v_min, v_max, code, a, N.stream_ptr(x))
     return out
 
 
@@ -334,8 +332,8 @@ def head_out(x: torch.Tensor, w: torch.Tensor, Ho: int, Wo: int, as_uint8: bool,
     B, H, W, hf = x.shape
     cout = int(w.shape[-1])
     out = torch.empty((B, Ho, Wo, cout), dtype=torch.uint8 if as_uint8 else torch.float32, device=x.device)
-    _call("bf_op_head_out", N.ptr(x), N.ptr(w), N.ptr(out), int(as_uint8), B, H, W, Ho, Wo, hf, cout, int(denormalize),
-          v_min, v_max, N.ptr(status), N.stream_ptr(x))
+    call("bf_op_head_out", N.ptr(x), N.ptr(w), N.ptr(out), int(as_uint8), B, H, W, Ho, Wo, hf, cout, int(denormalize),
+         v_min, v_max, N.ptr(status), N.stream_ptr(x))
     return out
 
 
@@ -348,15 +346,15 @@ def head_fused(x: torch.Tensor, gamma: Optional[torch.Tensor], w0p: torch.Tensor
     cout = int(w1.shape[-1])
     out = torch.empty((B, Ho, Wo, cout), dtype=torch.uint8 if as_uint8 else torch.float32, device=x.device)
     code, a = _act(act)
-    _call("bf_op_head_fused_h3" if arith == 1 and C in (32, 64) and hf == 32 else "bf_op_head_fused", N.ptr(x), N.ptr(gamma), eps,
-          N.ptr(w0p), code, a, N.ptr(w1), N.ptr(out), int(as_uint8), B, H, W, Ho, Wo, C, hf, cout, int(denormalize), v_min, v_max,
-          N.ptr(status), N.stream_ptr(x))
+    call("bf_op_head_fused_h3" if arith == 1 and C in (32, 64) and hf == 32 else "bf_op_head_fused", N.ptr(x), N.ptr(gamma), eps,
+         N.ptr(w0p), code, a, N.ptr(w1), N.ptr(out), int(as_uint8), B, H, W, Ho, Wo, C, hf, cout, int(denormalize), v_min, v_max,
+         N.ptr(status), N.stream_ptr(x))
     return out
 
 
 def channel_multiplier(w: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(w)
-    _call("bf_op_channel_multiplier", N.ptr(w), N.ptr(out), w.numel(), N.stream_ptr(w))
+    call("bf_op_channel_multiplier", N.ptr(w), N.ptr(out), w.numel(), N.stream_ptr(w))
     return out
 
 
@@ -372,45 +370,19 @@ def gaussian_kernel(kernel_size: Tuple[int, int]) -> np.ndarray:
 # the model
 # ---------------------------------------------------------------------------------------------
 
-class UnetLaplacianHydra:
+class UnetLaplacianHydra(OpGraphModel):
     """hydra(x) for backbone type "unet_laplacian": returns one denormalised output per scale, full resolution first
     (model.py:117-142).  Trainable tensors live in one flat float32 vector (`params`) in graph-construction order;
     `trainable_variables` lists (name, shape, kind, offset)."""
 
+    FAMILY = "unet_laplacian"
+    OPTIONS = ("arith", "fuse_up_block", "fuse_chain")       # see __init__
+    TRAINING_CALL = ("unet_laplacian: hydra(x, training=True) on its own is not built; the training step "
+                     "(forward + losses + gradients) is build_train_functions(...).train_step_single_gpu")
     multi_output = True           # DenoiserModule keeps output 0
     # True: when host arrays are handed back and the status word reports a non-finite value in front of a head's tanh (an
     # activation left the f16 range inside a split-f16 operator), switch to the exact-fp32 operators and repeat the call
     auto_exact_fallback = True
-
-    class _Desc:
-        def __init__(self, cin, cout):
-            self.in_channels, self.out_channels = cin, cout
-
-    def _status(self) -> torch.Tensor:
-        """int32 status word on the device, cleared (bf_op_fill32) at the start of a forward, OR-ed by the head kernels."""
-        if getattr(self, "_status_word", None) is None:
-            self._status_word = torch.empty(1, dtype=torch.int32, device=self.device)
-        _call("bf_op_fill32", N.ptr(self._status_word), 0, 1, N.stream_ptr(self._status_word))
-        return self._status_word
-
-    def status_tensor(self) -> Optional[torch.Tensor]:
-        return getattr(self, "_status_word", None)
-
-    def check_status(self, raise_on_overflow: bool = True) -> bool:
-        """synchronises and reads the status word of the last forward (see HydraModel.check_status)."""
-        st = self.status_tensor()
-        if st is None or not (int(st.item()) & N.BF_STATUS_F16_RANGE):
-            return True
-        if raise_on_overflow:
-            raise FloatingPointError("an activation left the f16 range inside the split-f16 operators; "
-                                     "call set_option('arith', 0) to run the exact-fp32 operators")
-        return False
-
-    def set_option(self, key: str, value: int):
-        if key not in ("arith", "fuse_up_block", "fuse_chain") or int(value) not in (0, 1):
-            raise ValueError(f"unknown option {key}={value}")
-        setattr(self, key, int(value))
-        self.version = getattr(self, "version", 0) + 1
 
     def __init__(self, config: Dict, device=None, seed: Optional[int] = None):
         bb, dn = config["backbone"], config["denoiser"]
@@ -427,8 +399,7 @@ class UnetLaplacianHydra:
         self.downsample_type = bb.get("downsample_type", "strides").strip().lower()
         if self.downsample_type not in ("strides", "conv2d", "maxpool"):
             raise ValueError(f"don't know how to handle [{self.downsample_type}]")          # downsampling.py:73-75
-        if dn.get("use_bn", False) or dn.get("use_ln", False) or dn.get("use_bias", False):
-            raise NotImplementedError("denoiser head: use_bn / use_ln / use_bias are outside the built graph")
+        self._refuse_head_options(dn)
         self.depth = int(bb.get("depth", 5))
         self.width = int(bb.get("width", 1) or 1)
         if self.width <= 0:
@@ -508,8 +479,6 @@ class UnetLaplacianHydra:
             raise NotImplementedError("unet_laplacian: use_concat without use_mix_project runs the first decoder block of a level on 2 C "
                                       "channels; the depthwise + LayerNorm operator takes up to 128")
 
-        self.desc = self._Desc(self.in_channels, self.out_channels)
-        self.device = torch.device(device) if device is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
         # 1: ConvNext MLPs with 32 / 64 channels on the f16 matrix cores with split-f16 operands (csrc/unet_h3.hip);
         # 0: every GEMM in exact fp32 (csrc/unet_ops.hip).  Same tests, same bars.
         self.arith = 1
@@ -519,10 +488,12 @@ class UnetLaplacianHydra:
         # 1: the pixel-wise decoder blocks of a 32-channel level (decoder_kernel_size 1) run up to three per launch, the level's node formed
         # on load (bf_op_convnext_chain32_h3); 0: one launch per block
         self.fuse_chain = 1
-        self._inventory = self._build_inventory()
-        self.n_params = sum(int(np.prod(s)) for _, s, _ in self._inventory)
-        self.params = torch.from_numpy(self._initial_values(seed)).to(self.device)
-        self._packed = None
+        self._init_storage(device, seed)
+
+    @staticmethod
+    def train_graph_class():
+        from .unet_train import UnetTrainGraph
+        return UnetTrainGraph
 
     @classmethod
     def from_keras_archive(cls, path: str, device=None) -> "UnetLaplacianHydra":
@@ -542,7 +513,8 @@ class UnetLaplacianHydra:
     def _is_attention(self, d: int) -> bool:
         return self.use_self_attention and d == self.depth - 1                    # :324
 
-    def _build_inventory(self) -> List[Tuple[str, Tuple[int, ...], str]]:
+    def _build_inventory(self) -> Tuple[List[Tuple[str, Tuple[int, ...], str]], List]:
+        """(trainable tensors, moving statistics: none in this graph)"""
         out = [("base/kernel", (5, 5, self.in_channels, self.filters), "conv")]
         A = self.filters
 
@@ -601,51 +573,23 @@ class UnetLaplacianHydra:
         for i in range(self.depth):
             out.append((f"head{i}/conv0/kernel", (1, 1, self.level_filters(i), self.head_filters), "conv"))
             out.append((f"head{i}/conv1/kernel", (1, 1, self.head_filters, self.out_channels), "conv"))
-        return out
+        return out, []
 
-    @property
-    def trainable_variables(self):
-        o, res = 0, []
-        for name, shape, kind in self._inventory:
-            res.append((name, shape, kind, o))
-            o += int(np.prod(shape))
-        return res
-
-    def count_params(self) -> int:
-        return self.n_params
-
-    def _initial_values(self, seed) -> np.ndarray:
+    def _initial_value(self, shape, kind: str, rng) -> np.ndarray:
         from .model import glorot_normal
-        rng = np.random.default_rng(seed)
-        parts = []
-        for _, shape, kind in self._inventory:
-            if kind in ("conv", "depthwise"):
-                a = glorot_normal(shape, rng)
-            elif kind == "ln_gamma":
-                a = np.ones(shape)
-            else:                                                # truncated_normal(0, 0.01) (custom_layers.py:271)
-                a = rng.normal(0.0, 0.01, shape)
-                bad = np.abs(a) > 0.02
-                while bad.any():
-                    a[bad] = rng.normal(0.0, 0.01, int(bad.sum()))
-                    bad = np.abs(a) > 0.02
-            parts.append(np.asarray(a, np.float32).ravel())
-        return np.concatenate(parts)
-
-    def mark_dirty(self):
-        """the flat parameter vector changed in place (optimizer step): drop the packed operands"""
-        self._packed = None
-        self.version = getattr(self, "version", 0) + 1
+        if kind in ("conv", "depthwise"):
+            return glorot_normal(shape, rng)
+        if kind == "ln_gamma":
+            return np.ones(shape)
+        a = rng.normal(0.0, 0.01, shape)                         # truncated_normal(0, 0.01) (custom_layers.py:271)
+        bad = np.abs(a) > 0.02
+        while bad.any():
+            a[bad] = rng.normal(0.0, 0.01, int(bad.sum()))
+            bad = np.abs(a) > 0.02
+        return a
 
     def get_weights(self) -> np.ndarray:
         return self.params.detach().cpu().numpy()
-
-    def set_weights(self, params: np.ndarray):
-        params = np.ascontiguousarray(params, np.float32).ravel()
-        if params.size != self.n_params:
-            raise ValueError(f"expected {self.n_params} parameters, got {params.size}")
-        self.params.copy_(torch.from_numpy(params))
-        self.mark_dirty()
 
     # -- packing -----------------------------------------------------------------------------
     def _pack(self) -> Dict[str, torch.Tensor]:
@@ -720,10 +664,6 @@ class UnetLaplacianHydra:
         return P
 
     # -- forward -----------------------------------------------------------------------------
-    def _require_gpu(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("unet_laplacian inference needs the GPU: there is no CPU execution path")
-
     def _fused_up_block(self, P, d: int, C: int, skip, low: torch.Tensor, up_act: str) -> bool:
         """the node enc + act(up(low)) can be formed inside the level's first decoder block (bf_op_convnext_block1_up_h3): 32 channels,
         split-f16 MLP, 1x1 depthwise, nothing between the Add and the block (no gate, no Concatenate, no mix projection)"""
@@ -768,7 +708,7 @@ class UnetLaplacianHydra:
                 acc = pointwise(hdn, w2p, 256, "linear", res=acc)
             out = torch.empty_like(x)
             B = x.shape[0]
-            _call("bf_op_scale_add", N.ptr(x), N.ptr(acc), N.ptr(mult), None, N.ptr(out), B, x.numel() // (B * 256), 256, N.stream_ptr(x))
+            call("bf_op_scale_add", N.ptr(x), N.ptr(acc), N.ptr(mult), None, N.ptr(out), B, x.numel() // (B * 256), 256, N.stream_ptr(x))
             return out
         if self.arith == 1 and f"{prefix}/mlp_h3" in P:
             return convnext_mlp_h3(t, x, P[f"{prefix}/mlp_h3"], mult, self.mlp_activation)
@@ -897,7 +837,7 @@ class UnetLaplacianHydra:
                 # first decoder block on the 2 C channels of Concatenate([enc, up]): depthwise + LayerNorm over 2 C, 1x1 2C -> 4C,
                 # 1x1 4C -> C, multiplier, NO skip (the channel counts differ: backbone_unet_laplacian.py:557-560)
                 cat = torch.empty(f.shape[:-1] + (2 * C,), dtype=torch.float32, device=f.device)
-                _call("bf_op_concat_channels", N.ptr(nodes[d]), N.ptr(f), None, N.ptr(cat), f.numel() // C, C, C, 0, N.stream_ptr(f))
+                call("bf_op_concat_channels", N.ptr(nodes[d]), N.ptr(f), None, N.ptr(cat), f.numel() // C, C, C, 0, N.stream_ptr(f))
                 pre = f"dec{d}_0"
                 t = dwconv_ln(cat, P[f"{pre}/dw/kernel"], P.get(f"{pre}/ln/gamma") if self.use_ln else None)
                 hdn = pointwise(t, P[f"{pre}/pw1/kernel"], 4 * C, self.mlp_activation)
@@ -945,48 +885,11 @@ class UnetLaplacianHydra:
         h = pointwise(f, P[f"head{i}/conv0/kernel"], self.head_filters, self.head_activation)
         return head_out(h, P[f"head{i}/conv1/kernel"], Ho, Wo, as_uint8, True, self.v_min, self.v_max, status=status)
 
-    def _as_device(self, x):
-        was_numpy = isinstance(x, np.ndarray)
-        if was_numpy:
-            x = torch.from_numpy(np.ascontiguousarray(x))
-        if x.dim() != 4 or x.shape[-1] != self.in_channels:
-            raise ValueError(f"expected [B,H,W,{self.in_channels}], got {tuple(x.shape)}")
-        if x.dtype != torch.uint8:
-            x = x.to(torch.float32)
-        return x.to(self.device).contiguous(), was_numpy
-
-    def __call__(self, x, training: bool = False):
-        """float32 (or uint8) [B,H,W,3] on the 0..255 scale -> list of float32 outputs, full resolution first."""
-        if training:
-            raise NotImplementedError("unet_laplacian: hydra(x, training=True) on its own is not built; the training step "
-                                      "(forward + losses + gradients) is build_train_functions(...).train_step_single_gpu")
-        self._require_gpu()
-        x, was_numpy = self._as_device(x)
-        B, H, W, _ = x.shape
-        P = self._pack()
-        outs = []
-        status = self._status()
-        for i, f in enumerate(self.backbone(x, H, W, defer_output_norm=True)):
-            outs.append(self._head(P, i, f, f.shape[1], f.shape[2], False, deferred_norm=True, status=status))
-        if was_numpy:
-            torch.cuda.synchronize(self.device)
-            if not self.check_status(raise_on_overflow=not (self.auto_exact_fallback and self.arith != 0)):
-                self.set_option("arith", 0)
-                return self(x.cpu().numpy())
-            return [o.cpu().numpy() for o in outs]
-        return outs
-
-    def predict(self, x):
-        return self(x)
-
-    def infer_u8(self, image: torch.Tensor, cast_to_uint8: bool = True) -> torch.Tensor:
-        """DenoiserModule.__call__ for this model (module_denoiser.py:46-75): pad to a power of two, hydra, first output,
-        crop, round half to even, cast.  Only the full-resolution head is evaluated."""
-        from .utilities import next_power_of_2
-        self._require_gpu()
-        B, Hs, Ws, _ = image.shape
-        H, W = next_power_of_2(Hs), next_power_of_2(Ws)
+    def _outputs(self, x: torch.Tensor, H: int, W: int, crop=None, as_uint8: bool = False):
+        """every scale's output, or with crop = (Ho, Wo) only the full-resolution head's (cropped)"""
         P = self._pack()
         status = self._status()
-        f = self.backbone(image, H, W, defer_output_norm=True)[0]
-        return self._head(P, 0, f, Hs, Ws, cast_to_uint8, deferred_norm=True, status=status)
+        fs = self.backbone(x, H, W, defer_output_norm=True)
+        if crop is not None:
+            return self._head(P, 0, fs[0], crop[0], crop[1], as_uint8, deferred_norm=True, status=status)
+        return [self._head(P, i, f, f.shape[1], f.shape[2], False, deferred_norm=True, status=status) for i, f in enumerate(fs)]

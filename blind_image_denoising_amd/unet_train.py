@@ -26,7 +26,9 @@ import torch
 
 from . import _native as N
 from . import unet_laplacian as UL
+from ._native import call
 from .pyramid import avg_pool2_valid, upsample_2x
+from .train_graph import TrainGraph, pack
 
 SOFTORTHONORMAL = (0.01, 0.0, 1e-4)        # bfcnn/constants.py:19-21: lambda, l1, l2
 MULTIPLIER_L1 = 1e-6                        # ChannelLearnableMultiplier's regulariser (custom_layers.py:267)
@@ -34,89 +36,11 @@ KERNEL_L2 = 0.01                            # keras "l2" string regulariser
 GATE_L2 = 1e-4                              # AdditiveAttentionGate's default kernel regulariser (custom_layers.py:726)
 
 
-def _call(fn_name: str, *args):
-    N.check(getattr(N.lib(), fn_name)(*args), None, fn_name)
-
-
-class _Ops:
-    """the backward primitives as tensor-in / tensor-out calls sharing one scratch buffer"""
-
-    def __init__(self, device, scratch_floats: int):
-        self.device = device
-        self.scratch = torch.empty(int(scratch_floats), dtype=torch.float32, device=device)
-
-    def _s(self):
-        return N.ptr(self.scratch), self.scratch.numel()
-
-    def act_bwd(self, out, dy, act, pre=None):
-        """dy * act'(.): from the activation's OUTPUT for the sign-preserving ones, from its input `pre` for GELU"""
-        code, a = UL._act(act)
-        if code == 0:
-            return dy
-        dx = torch.empty_like(dy)
-        if code == 3:
-            if pre is None:
-                raise ValueError("the GELU derivative needs the pre-activation")
-            _call("bf_op_act_bwd", N.ptr(pre), N.ptr(dy), N.ptr(dx), dy.numel(), code, a, 0, N.stream_ptr(dy))
-        else:
-            _call("bf_op_act_bwd", N.ptr(out), N.ptr(dy), N.ptr(dx), dy.numel(), code, a, 1, N.stream_ptr(dy))
-        return dx
-
-    def act_bwd_alpha(self, out, dy, alpha):
-        dx = torch.empty_like(dy)
-        _call("bf_op_act_bwd", N.ptr(out), N.ptr(dy), N.ptr(dx), dy.numel(), 2, float(alpha), 1, N.stream_ptr(dy))
-        return dx
-
-    def matmul_wgrad(self, x, dy, dw):
-        cin, cout = x.shape[-1], dy.shape[-1]
-        sp, sn = self._s()
-        _call("bf_op_matmul_wgrad", N.ptr(x), N.ptr(dy), N.ptr(dw), x.numel() // cin, cin, cout, sp, sn, N.stream_ptr(x))
-
-    def dwconv_wgrad(self, x, dy, dw, k):
-        B, H, W, Cc = x.shape
-        sp, sn = self._s()
-        _call("bf_op_dwconv_wgrad", N.ptr(x), N.ptr(dy), N.ptr(dw), B, H, W, Cc, k, sp, sn, N.stream_ptr(x))
-
-    def layernorm_bwd(self, x, gamma, dy, dgamma):
-        Cc = x.shape[-1]
-        dx = torch.empty_like(x)
-        sp, sn = self._s()
-        _call("bf_op_layernorm_bwd", N.ptr(x), N.ptr(gamma), N.ptr(dy), N.ptr(dx), N.ptr(dgamma), x.numel() // Cc, Cc, UL.LN_EPSILON,
-              sp, sn, N.stream_ptr(x))
-        return dx
-
-    def scale_add(self, res, t, m, s):
-        B = t.shape[0]
-        Cc = t.shape[-1]
-        out = torch.empty_like(t)
-        _call("bf_op_scale_add", N.ptr(res), N.ptr(t), N.ptr(m), N.ptr(s), N.ptr(out), B, t.numel() // (B * Cc), Cc, N.stream_ptr(t))
-        return out
-
-    def scale_add_bwd(self, t, m, s, dy, dm):
-        B, Cc = t.shape[0], t.shape[-1]
-        dt = torch.empty_like(t)
-        sp, sn = self._s()
-        _call("bf_op_scale_add_bwd", N.ptr(t), N.ptr(m), N.ptr(s), N.ptr(dy), N.ptr(dt), N.ptr(dm), B, t.numel() // (B * Cc), Cc,
-              sp, sn, N.stream_ptr(t))
-        return dt
-
-    def add(self, a, b):
-        """a + b (new tensor)"""
-        return self.scale_add(a, b, None, None)
-
-    def transpose(self, w2d):
-        a, b = w2d.shape
-        out = torch.empty((b, a), dtype=torch.float32, device=w2d.device)
-        _call("bf_op_transpose2d", N.ptr(w2d), N.ptr(out), a, b, N.stream_ptr(w2d))
-        return out
-
-
-class UnetTrainGraph:
+class UnetTrainGraph(TrainGraph):
     """train_step_single_gpu for a UnetLaplacianHydra: `step(gt, noisy, depth_weights, ...)` returns the per-scale predictions
     and fills `grads` (flat, laid out like model.params) and the loss slots."""
 
     def __init__(self, model: "UL.UnetLaplacianHydra", loss_config: Dict, soft_orthonormal: Optional[bool] = None):
-        self.m = model
         bad = []
         if model.downsample_type not in ("strides", "conv2d", "maxpool"): bad.append(f"downsample_type {model.downsample_type}")
         if model.upsample_type not in ("upsample_laplacian_conv2d", "upsample_nearest_conv2d", "upsample_bilinear_conv2d", "bilinear",
@@ -130,57 +54,24 @@ class UnetTrainGraph:
             bad.append("a 256-channel ConvNext level (runs at inference only)")
         if bad:
             raise NotImplementedError("unet_laplacian training is built for the configs/unet_laplacian_v5.json graph family: " + ", ".join(bad))
-        self.loss_config = dict(loss_config)
+        super().__init__(model, loss_config)
         bb = model.config["backbone"]
         self.soft_orthonormal = bool(bb.get("use_soft_orthonormal_regularization", False)) if soft_orthonormal is None else soft_orthonormal
-        self.off = {name: (off, shape, kind) for name, shape, kind, off in model.trainable_variables}
-        self.ops = None
-        self.totals = None
-
-    # ---- parameters ------------------------------------------------------------------------------------------------------
-    def W(self, name) -> torch.Tensor:
-        off, shape, _ = self.off[name]
-        n = int(np.prod(shape))
-        t = self.m.params[off:off + n]
-        if off % 4:
-            t = t.clone()
-        return t.view(shape)
-
-    def G(self, name, grads) -> torch.Tensor:
-        """the slice of the flat gradient a tensor's gradient is written to (16-byte aligned staging when the slice is not)"""
-        off, shape, _ = self.off[name]
-        n = int(np.prod(shape))
-        if off % 4:
-            buf = torch.empty(n, dtype=torch.float32, device=grads.device)
-            self._unaligned.append((buf, off, n))
-            return buf
-        return grads[off:off + n]
 
     # ---- one training step ----------------------------------------------------------------------------------------------------
     def step(self, gt: torch.Tensor, noisy: torch.Tensor, depth_weights: Sequence[float], grads: torch.Tensor,
              depth_scale: Optional[Dict[str, torch.Tensor]] = None, attn_scale: Optional[Dict[str, torch.Tensor]] = None):
         m = self.m
         dev = m.device
-        gt = gt.to(device=dev, dtype=torch.float32).contiguous()
-        noisy = noisy.to(device=dev).contiguous()
-        if noisy.dtype != torch.uint8:
-            noisy = noisy.to(torch.float32)
+        gt, noisy = self._inputs(gt, noisy)
         B, H, Wd, _ = noisy.shape
         if H % (1 << (m.depth - 1)) or Wd % (1 << (m.depth - 1)):
             raise ValueError(f"training needs sizes divisible by {1 << (m.depth - 1)} (got {H}x{Wd})")
         depth_scale, attn_scale = depth_scale or {}, attn_scale or {}
         npix0 = B * H * Wd
-        need = max(8 * 1024 * 1024, int(N.lib().bf_op_denoiser_loss_scratch_floats(B, H, Wd, m.out_channels)) + 1024,
-                   B * 256 * 256 + 1024, npix0 * 4)
-        if self.ops is None or self.ops.scratch.numel() < need:
-            self.ops = _Ops(dev, need)
-        ops = self.ops
-        self._unaligned = []
+        ops = self._begin(grads, max(8 * 1024 * 1024, int(N.lib().bf_op_denoiser_loss_scratch_floats(B, H, Wd, m.out_channels)) + 1024,
+                                     B * 256 * 256 + 1024, npix0 * 4))
         a = m.activation
-        back = []                          # closures, run in reverse
-
-        def pack(w2d):
-            return UL.pack_pointwise(w2d.contiguous())
 
         def pointwise_act(x_, wp, cout, act, alpha=None):
             """(act(x W), what its derivative is taken from): the fused epilogue for the sign-preserving activations, the
@@ -225,8 +116,8 @@ class UnetTrainGraph:
                 dm = torch.empty(Cc, dtype=torch.float32, device=dev) if m.use_gamma else None
                 dt4 = ops.scale_add_bwd(t4, mult, s, dout, dm)
                 if m.use_gamma:
-                    _call("bf_op_multiplier_bwd", N.ptr(wm), N.ptr(dm), N.ptr(self.G(f"{prefix}/gamma/w", grads)), Cc, N.stream_ptr(dm))
-                gw2, gw1 = self.G(f"{prefix}/pw2/kernel", grads).view(Hh, Cc), self.G(f"{prefix}/pw1/kernel", grads).view(Cin, Hh)
+                    call("bf_op_multiplier_bwd", N.ptr(wm), N.ptr(dm), N.ptr(self.G(f"{prefix}/gamma/w")), Cc, N.stream_ptr(dm))
+                gw2, gw1 = self.G(f"{prefix}/pw2/kernel").view(Hh, Cc), self.G(f"{prefix}/pw1/kernel").view(Cin, Hh)
                 dt2 = None
                 for j in chunks:
                     ops.matmul_wgrad(t3[j], dt4, gw2[j * Hc:(j + 1) * Hc])
@@ -238,10 +129,10 @@ class UnetTrainGraph:
                         ops.matmul_wgrad(t2, dt3, blk)
                         gw1[:, j * Hc:(j + 1) * Hc].copy_(blk)
                     dt2 = UL.pointwise(dt3, pack(ops.transpose(w1c[j])), Cin, res=dt2)
-                dt1 = ops.layernorm_bwd(t1, gamma, dt2, self.G(f"{prefix}/ln/gamma", grads)) if m.use_ln else dt2
-                ops.dwconv_wgrad(x, dt1, self.G(f"{prefix}/dw/kernel", grads), k)
+                dt1 = ops.layernorm_bwd(t1, gamma, dt2, self.G(f"{prefix}/ln/gamma")) if m.use_ln else dt2
+                ops.dwconv_wgrad(x, dt1, self.G(f"{prefix}/dw/kernel"), k)
                 wf = torch.empty_like(wdw)
-                _call("bf_op_flip_hw", N.ptr(wdw), N.ptr(wf), k, Cin, N.stream_ptr(wdw))
+                call("bf_op_flip_hw", N.ptr(wdw), N.ptr(wf), k, Cin, N.stream_ptr(wdw))
                 dx = UL.dwconv_mult(dt1, wf, None)
                 return ops.add(dout, dx) if skip else dx
             return out, bwd
@@ -265,7 +156,7 @@ class UnetTrainGraph:
             ps = attn_scale.get(prefix)
             o = torch.empty((NB, T, A), dtype=torch.float32, device=dev)
             P = torch.empty((NB, T, T), dtype=torch.float32, device=dev)
-            _call("bf_op_attention_train", N.ptr(q), N.ptr(v), N.ptr(k_), N.ptr(ps), N.ptr(o), N.ptr(P), NB, T, A, N.stream_ptr(q))
+            call("bf_op_attention_train", N.ptr(q), N.ptr(v), N.ptr(k_), N.ptr(ps), N.ptr(o), N.ptr(P), NB, T, A, N.stream_ptr(q))
             o4 = o.view(Bc, rh, rw, A)
             gamma1 = self.W(f"{prefix}/ln1/gamma") if (rows and m.use_ln) else None
             if rows:
@@ -282,29 +173,29 @@ class UnetTrainGraph:
             def bwd(dout):
                 dm = torch.empty(Cc, dtype=torch.float32, device=dev)
                 dt = ops.scale_add_bwd(t, mult, s, dout, dm)
-                _call("bf_op_multiplier_bwd", N.ptr(wm), N.ptr(dm), N.ptr(self.G(f"{prefix}/gamma/w", grads)), Cc, N.stream_ptr(dm))
-                ops.matmul_wgrad(u, dt, self.G(f"{prefix}/out/kernel", grads))
+                call("bf_op_multiplier_bwd", N.ptr(wm), N.ptr(dm), N.ptr(self.G(f"{prefix}/gamma/w")), Cc, N.stream_ptr(dm))
+                ops.matmul_wgrad(u, dt, self.G(f"{prefix}/out/kernel"))
                 du = UL.pointwise(dt, pack(ops.transpose(wo)), A)
                 if rows:
-                    do = ops.layernorm_bwd(o4, gamma1, du, self.G(f"{prefix}/ln1/gamma", grads)) if m.use_ln else du
+                    do = ops.layernorm_bwd(o4, gamma1, du, self.G(f"{prefix}/ln1/gamma")) if m.use_ln else du
                 else:
                     do = torch.empty((Bc, rh, rw, A), dtype=torch.float32, device=dev)
-                    _call("bf_op_resize_bilinear_bwd", N.ptr(du), N.ptr(do), Bc, rh, rw, A, Hc, Wc, N.ptr(ops.scratch), N.stream_ptr(du))
+                    call("bf_op_resize_bilinear_bwd", N.ptr(du), N.ptr(do), Bc, rh, rw, A, Hc, Wc, N.ptr(ops.scratch), N.stream_ptr(du))
                 dq, dv, dk = (torch.empty((NB, T, A), dtype=torch.float32, device=dev) for _ in range(3))
                 dS = torch.empty((NB, T, T), dtype=torch.float32, device=dev)
-                _call("bf_op_attention_bwd", N.ptr(q), N.ptr(v), N.ptr(k_), N.ptr(ps), N.ptr(P), N.ptr(do), N.ptr(dq), N.ptr(dv),
-                      N.ptr(dk), N.ptr(dS), NB, T, A, N.stream_ptr(q))
+                call("bf_op_attention_bwd", N.ptr(q), N.ptr(v), N.ptr(k_), N.ptr(ps), N.ptr(P), N.ptr(do), N.ptr(dq), N.ptr(dv),
+                     N.ptr(dk), N.ptr(dS), NB, T, A, N.stream_ptr(q))
                 dn = None
                 for name, y, ypre, dy in zip(order, (q, v, k_), (qpre, vpre, kpre), (dq, dv, dk)):
                     dp = (ops.act_bwd_alpha(y, dy, alpha) if alpha is not None else ops.act_bwd(y, dy, qact, ypre)).view(Bc, rh, rw, A)
-                    ops.matmul_wgrad(n_, dp, self.G(f"{prefix}/{name}/kernel", grads))
+                    ops.matmul_wgrad(n_, dp, self.G(f"{prefix}/{name}/kernel"))
                     part = UL.pointwise(dp, pack(ops.transpose(ws[name])), Cc)
                     dn = part if dn is None else ops.add(dn, part)
-                dr = ops.layernorm_bwd(r, gamma, dn, self.G(f"{prefix}/ln/gamma", grads)) if m.use_ln else dn
+                dr = ops.layernorm_bwd(r, gamma, dn, self.G(f"{prefix}/ln/gamma")) if m.use_ln else dn
                 if rows:
                     return ops.add(dout, dr)
                 dxb = torch.empty_like(x)
-                _call("bf_op_resize_bilinear_bwd", N.ptr(dr), N.ptr(dxb), Bc, Hc, Wc, Cc, rh, rw, N.ptr(ops.scratch), N.stream_ptr(dr))
+                call("bf_op_resize_bilinear_bwd", N.ptr(dr), N.ptr(dxb), Bc, Hc, Wc, Cc, rh, rw, N.ptr(ops.scratch), N.stream_ptr(dr))
                 return ops.add(dout, dxb)
             return out, bwd
 
@@ -314,7 +205,7 @@ class UnetTrainGraph:
             y = UL.dwconv_ln(x, None, gamma, act)
 
             def bwd(dy):
-                return ops.layernorm_bwd(x, gamma, ops.act_bwd(y, dy, act), self.G(name, grads))
+                return ops.layernorm_bwd(x, gamma, ops.act_bwd(y, dy, act), self.G(name))
             return y, bwd
 
         def conv1x1_act(name, x, cout, act):
@@ -324,7 +215,7 @@ class UnetTrainGraph:
 
             def bwd(dy):
                 dp = ops.act_bwd(y, dy, act)
-                ops.matmul_wgrad(x, dp, self.G(name, grads))
+                ops.matmul_wgrad(x, dp, self.G(name))
                 return UL.pointwise(dp, pack(ops.transpose(w)), cin)
             return y, bwd
 
@@ -337,13 +228,13 @@ class UnetTrainGraph:
             def bwd(dy):
                 dp = ops.act_bwd(y, dy, act)
                 sp, sn = ops._s()
-                _call("bf_op_conv2d_wgrad", N.ptr(x), 0, N.ptr(dp), N.ptr(self.G(name, grads)), Bc, Hc, Wc, cin, cout, 3, 0, 0.0, 0.0, sp, sn,
-                      N.stream_ptr(dp))
+                call("bf_op_conv2d_wgrad", N.ptr(x), 0, N.ptr(dp), N.ptr(self.G(name)), Bc, Hc, Wc, cin, cout, 3, 0, 0.0, 0.0, sp, sn,
+                     N.stream_ptr(dp))
                 wf = torch.empty_like(w)                                          # data gradient: taps flipped, every tap transposed
-                _call("bf_op_flip_hw", N.ptr(w), N.ptr(wf), 3, cin * cout, N.stream_ptr(w))
+                call("bf_op_flip_hw", N.ptr(w), N.ptr(wf), 3, cin * cout, N.stream_ptr(w))
                 wt = torch.empty((3, 3, cout, cin), dtype=torch.float32, device=dev)
                 for t_ in range(9):
-                    _call("bf_op_transpose2d", N.ptr(wf.view(9, cin, cout)[t_]), N.ptr(wt.view(9, cout, cin)[t_]), cin, cout, N.stream_ptr(wf))
+                    call("bf_op_transpose2d", N.ptr(wf.view(9, cin, cout)[t_]), N.ptr(wt.view(9, cout, cin)[t_]), cin, cout, N.stream_ptr(wf))
                 return UL.conv2d(dp, UL.pack_conv(wt), cin, 3, 1, "linear")
             return y, bwd
 
@@ -359,13 +250,13 @@ class UnetTrainGraph:
 
             def bwd(dy):
                 dp = ops.act_bwd(y, dy, act)
-                gw = self.G(name, grads).view(4, cin * cout)
+                gw = self.G(name).view(4, cin * cout)
                 xs = torch.empty((Bc, Hc // 2, Wc // 2, cin), dtype=torch.float32, device=dev)
                 flat = x.reshape(-1)
                 for ky in range(2):
                     for kx in range(2):
                         src = flat[(ky * Wc + kx) * cin:]                         # x[:, ky::2, kx::2, :] as a strided slice from a shifted base
-                        _call("bf_strided_slice2", N.ptr(src), N.ptr(xs), Bc, Hc, Wc, cin, N.stream_ptr(x))
+                        call("bf_strided_slice2", N.ptr(src), N.ptr(xs), Bc, Hc, Wc, cin, N.stream_ptr(x))
                         ops.matmul_wgrad(xs, dp, gw[ky * 2 + kx])
                 return UL.conv2d_transpose(dp, w.contiguous(), 2, "linear")     # keras Conv2D kernel [k,k,cin,cout] = Conv2DTranspose's [k,k,out,in]
             return y, bwd
@@ -388,22 +279,22 @@ class UnetTrainGraph:
             mult = UL.channel_multiplier(wm)
             o = ops.scale_add(None, o_raw, mult, None)
             out = torch.empty_like(enc)
-            _call("bf_op_sigmoid_gate", N.ptr(enc), N.ptr(o), N.ptr(up), N.ptr(out), enc.numel(), N.stream_ptr(enc))
+            call("bf_op_sigmoid_gate", N.ptr(enc), N.ptr(o), N.ptr(up), N.ptr(out), enc.numel(), N.stream_ptr(enc))
 
             def bwd(dout):
                 denc, do = torch.empty_like(enc), torch.empty_like(enc)
-                _call("bf_op_sigmoid_gate_bwd", N.ptr(enc), N.ptr(o), N.ptr(dout), N.ptr(denc), N.ptr(do), enc.numel(), N.stream_ptr(enc))
+                call("bf_op_sigmoid_gate_bwd", N.ptr(enc), N.ptr(o), N.ptr(dout), N.ptr(denc), N.ptr(do), enc.numel(), N.stream_ptr(enc))
                 dm = torch.empty(Cc, dtype=torch.float32, device=dev)
                 do_raw = ops.scale_add_bwd(o_raw, mult, None, do, dm)
-                _call("bf_op_multiplier_bwd", N.ptr(wm), N.ptr(dm), N.ptr(self.G(f"{pre}/scale/w", grads)), Cc, N.stream_ptr(dm))
-                ops.matmul_wgrad(sact, do_raw, self.G(f"{pre}/o/kernel", grads))
+                call("bf_op_multiplier_bwd", N.ptr(wm), N.ptr(dm), N.ptr(self.G(f"{pre}/scale/w")), Cc, N.stream_ptr(dm))
+                ops.matmul_wgrad(sact, do_raw, self.G(f"{pre}/o/kernel"))
                 dz = ops.act_bwd(sact, UL.pointwise(do_raw, pack(ops.transpose(wo)), Cc), "leaky_relu_01")
-                ops.matmul_wgrad(lx, dz, self.G(f"{pre}/x/kernel", grads))
-                ops.matmul_wgrad(ly, dz, self.G(f"{pre}/y/kernel", grads))
+                ops.matmul_wgrad(lx, dz, self.G(f"{pre}/x/kernel"))
+                ops.matmul_wgrad(ly, dz, self.G(f"{pre}/y/kernel"))
                 dlx = UL.pointwise(dz, pack(ops.transpose(wx)), Cc)
                 dly = UL.pointwise(dz, pack(ops.transpose(wy)), Cc)
-                dup = ops.layernorm_bwd(up, gx, dlx, self.G(f"{pre}/x_ln/gamma", grads)) if m.use_ln else dlx
-                dency = ops.layernorm_bwd(enc, gy, dly, self.G(f"{pre}/y_ln/gamma", grads)) if m.use_ln else dly
+                dup = ops.layernorm_bwd(up, gx, dlx, self.G(f"{pre}/x_ln/gamma")) if m.use_ln else dlx
+                dency = ops.layernorm_bwd(enc, gy, dly, self.G(f"{pre}/y_ln/gamma")) if m.use_ln else dly
                 return ops.add(denc, dency), ops.add(dout, dup)
             return out, bwd
 
@@ -415,8 +306,8 @@ class UnetTrainGraph:
         def base_bwd(dx):
             dpre = ops.act_bwd(x0, dx, a)
             sp, sn = ops._s()
-            _call("bf_op_conv2d_wgrad", N.ptr(noisy), int(noisy.dtype == torch.uint8), N.ptr(dpre), N.ptr(self.G("base/kernel", grads)),
-                  B, H, Wd, m.in_channels, m.filters, 5, 1, m.v_min, m.v_max, sp, sn, N.stream_ptr(dpre))
+            call("bf_op_conv2d_wgrad", N.ptr(noisy), int(noisy.dtype == torch.uint8), N.ptr(dpre), N.ptr(self.G("base/kernel")),
+                 B, H, Wd, m.in_channels, m.filters, 5, 1, m.v_min, m.v_max, sp, sn, N.stream_ptr(dpre))
             return None
         # gradient bookkeeping: `flow` is a list of (forward value, backward closure chain); the graph below is a chain per
         # level with two fan-outs (the Laplacian split; the level outputs feeding a head and the next decoder level)
@@ -453,8 +344,8 @@ class UnetTrainGraph:
                     def b_(dy, down=down, b_c=b_c):
                         dmp = b_c(dy)
                         dd = torch.empty_like(down)
-                        _call("bf_op_maxpool2_bwd", N.ptr(down), N.ptr(dmp), N.ptr(dd), down.shape[0], down.shape[1], down.shape[2],
-                              down.shape[3], N.stream_ptr(dmp))
+                        call("bf_op_maxpool2_bwd", N.ptr(down), N.ptr(dmp), N.ptr(dd), down.shape[0], down.shape[1], down.shape[2],
+                             down.shape[3], N.stream_ptr(dmp))
                         return dd
                 else:
                     x, b_ = conv2x2_s2_act(f"down{d}/kernel", down, m.level_filters(d + 1), a)
@@ -488,7 +379,7 @@ class UnetTrainGraph:
                 x, b_gate = attention_gate(d, lap[d], up)
             elif m.use_concat:                                                # Concatenate([encoder feature, upsampled]) (:516-517)
                 x = torch.empty(up.shape[:-1] + (2 * Cc,), dtype=torch.float32, device=dev)
-                _call("bf_op_concat_channels", N.ptr(lap[d]), N.ptr(up), None, N.ptr(x), up.numel() // Cc, Cc, Cc, 0, N.stream_ptr(up))
+                call("bf_op_concat_channels", N.ptr(lap[d]), N.ptr(up), None, N.ptr(x), up.numel() // Cc, Cc, Cc, 0, N.stream_ptr(up))
             else:
                 x = ops.add(lap[d], up)
             chain = [("up", b_up, low.shape, bil, b_gate, conv_first)]
@@ -505,12 +396,7 @@ class UnetTrainGraph:
             dec_chain[d] = chain
 
         # heads + losses
-        ld = N.LossDesc()
-        ld.struct_size = C.sizeof(N.LossDesc)
-        lc = self.loss_config
-        ld.hinge, ld.cutoff = float(lc.get("hinge", 0.0)), float(lc.get("cutoff", 255.0))
-        ld.mae_multiplier, ld.mse_multiplier = float(lc.get("mae_multiplier", 1.0)), float(lc.get("mse_multiplier", 0.0))
-        ld.ssim_multiplier, ld.regularization = float(lc.get("ssim_multiplier", 1.0)), float(lc.get("regularization", 1.0))
+        ld = self.ld = self._loss_desc(1.0)
         gts = [gt]
         for _ in range(m.depth - 1):
             gts.append(avg_pool2_valid(gts[-1], clip_values=True, round_values=True))       # multiscales_generator_fn
@@ -530,16 +416,16 @@ class UnetTrainGraph:
             dpred = torch.empty_like(pred)
             ld.depth_weight = float(depth_weights[i])
             sp, sn = ops._s()
-            _call("bf_op_denoiser_loss", N.ptr(pred), N.ptr(gts[i]), Bc, Hc, Wc, m.out_channels, C.byref(ld), N.ptr(dpred), N.ptr(losses),
-                  sp, sn, N.stream_ptr(pred))
+            call("bf_op_denoiser_loss", N.ptr(pred), N.ptr(gts[i]), Bc, Hc, Wc, m.out_channels, C.byref(ld), N.ptr(dpred), N.ptr(losses),
+                 sp, sn, N.stream_ptr(pred))
             scale_losses.append(losses)
-            _call("bf_op_axpy", N.ptr(total), N.ptr(losses[N.BF_LOSS_TOTAL:N.BF_LOSS_TOTAL + 1]), 1.0, 0, 1, N.stream_ptr(total))
+            call("bf_op_axpy", N.ptr(total), N.ptr(losses[N.BF_LOSS_TOTAL:N.BF_LOSS_TOTAL + 1]), 1.0, 0, 1, N.stream_ptr(total))
             dh0 = torch.empty_like(h0)
             sp, sn = ops._s()
-            _call("bf_op_head_out_bwd", N.ptr(h0), N.ptr(w1), N.ptr(dpred), N.ptr(dh0), N.ptr(self.G(f"head{i}/conv1/kernel", grads)),
-                  Bc * Hc * Wc, m.head_filters, m.out_channels, 1, m.v_min, m.v_max, sp, sn, N.stream_ptr(h0))
+            call("bf_op_head_out_bwd", N.ptr(h0), N.ptr(w1), N.ptr(dpred), N.ptr(dh0), N.ptr(self.G(f"head{i}/conv1/kernel")),
+                 Bc * Hc * Wc, m.head_filters, m.out_channels, 1, m.v_min, m.v_max, sp, sn, N.stream_ptr(h0))
             dh0p = ops.act_bwd(h0, dh0, m.head_activation)
-            ops.matmul_wgrad(f, dh0p, self.G(f"head{i}/conv0/kernel", grads))
+            ops.matmul_wgrad(f, dh0p, self.G(f"head{i}/conv0/kernel"))
             dfeat[i] = UL.pointwise(dh0p, pack(ops.transpose(w0)), Cc)
             if b_head_ln is not None:
                 dfeat[i] = b_head_ln(dfeat[i])
@@ -560,19 +446,19 @@ class UnetTrainGraph:
                 Ch = g.shape[-1] // 2
                 halves = [torch.empty(g.shape[:-1] + (Ch,), dtype=torch.float32, device=dev) for _ in range(2)]
                 for h_, o_ in zip(halves, (0, Ch)):
-                    _call("bf_op_slice_channels", N.ptr(g), N.ptr(h_), g.numel() // (2 * Ch), 2 * Ch, o_, Ch, N.stream_ptr(g))
+                    call("bf_op_slice_channels", N.ptr(g), N.ptr(h_), g.numel() // (2 * Ch), 2 * Ch, o_, Ch, N.stream_ptr(g))
                 dlap[d], g = halves
             else:
                 dlap[d] = g                                             # x = lap[d] + up
             if conv_first:                                              # up = resize(conv(low))
                 dc = torch.empty(tuple(low_shape[:3]) + (g.shape[-1],), dtype=torch.float32, device=dev)
-                _call("bf_op_upsample2x_bwd", N.ptr(g), N.ptr(dc), low_shape[0], low_shape[1], low_shape[2], g.shape[-1], 1, N.stream_ptr(g))
+                call("bf_op_upsample2x_bwd", N.ptr(g), N.ptr(dc), low_shape[0], low_shape[1], low_shape[2], g.shape[-1], 1, N.stream_ptr(g))
                 dlow[d + 1] = b_up(dc)
                 continue
             du2 = b_up(g)
             dl = torch.empty(low_shape, dtype=torch.float32, device=dev)
-            _call("bf_op_upsample2x_bwd", N.ptr(du2), N.ptr(dl), low_shape[0], low_shape[1], low_shape[2], low_shape[3], int(bil),
-                  N.stream_ptr(du2))
+            call("bf_op_upsample2x_bwd", N.ptr(du2), N.ptr(dl), low_shape[0], low_shape[1], low_shape[2], low_shape[3], int(bil),
+                 N.stream_ptr(du2))
             dlow[d + 1] = dl
         last = m.depth - 1
         g = dfeat[last] if last not in dlow else ops.add(dfeat[last], dlow[last])
@@ -582,8 +468,8 @@ class UnetTrainGraph:
             else:                                                      # the split of level d: g = d(down), dlap[d] = d(lap)
                 _, d, (Bx, Hx, Wx, Cx), ds = item
                 dx = torch.empty((Bx, Hx, Wx, Cx), dtype=torch.float32, device=dev)
-                _call("bf_op_smooth_split_bwd_ex", N.ptr(dlap[d]), N.ptr(g), N.ptr(gauss), N.ptr(dx), Bx, Hx, Wx, Cx, k_g, ds,
-                      N.stream_ptr(g))
+                call("bf_op_smooth_split_bwd_ex", N.ptr(dlap[d]), N.ptr(g), N.ptr(gauss), N.ptr(dx), Bx, Hx, Wx, Cx, k_g, ds,
+                     N.stream_ptr(g))
                 g = dx
         base_bwd(g)
 
@@ -594,31 +480,19 @@ class UnetTrainGraph:
             if kind == "ln_gamma":
                 continue
             n = int(np.prod(shape))
-            gslice = self._grad_view(name, grads)
+            gslice = self._grad_view(name)
             w = self.W(name)
             leaf = name.split("/")[1]
             is_gate = name.startswith("gate")            # AdditiveAttentionGate convolutions: soft-orthonormal with the flag, else l2(1e-4)
             soft = leaf in ("key", "query", "value", "out") or (leaf in ("pw1", "pw2") and self.soft_orthonormal) or \
                 (is_gate and kind == "conv" and self.soft_orthonormal)
             if kind == "multiplier":
-                _call("bf_op_reg_elementwise", N.ptr(w), N.ptr(gslice), n, N.BF_REG_L1, MULTIPLIER_L1, reg, N.ptr(total[1:2]), N.stream_ptr(w))
+                call("bf_op_reg_elementwise", N.ptr(w), N.ptr(gslice), n, N.BF_REG_L1, MULTIPLIER_L1, reg, N.ptr(total[1:2]), N.stream_ptr(w))
             elif soft:
-                _call("bf_op_reg_soft_orthonormal", N.ptr(w), N.ptr(gslice), shape[2], shape[3], SOFTORTHONORMAL[0], SOFTORTHONORMAL[1],
-                      SOFTORTHONORMAL[2], reg, N.ptr(total[1:2]), N.ptr(sob), N.stream_ptr(w))
+                call("bf_op_reg_soft_orthonormal", N.ptr(w), N.ptr(gslice), shape[2], shape[3], SOFTORTHONORMAL[0], SOFTORTHONORMAL[1],
+                     SOFTORTHONORMAL[2], reg, N.ptr(total[1:2]), N.ptr(sob), N.stream_ptr(w))
             else:
-                _call("bf_op_reg_elementwise", N.ptr(w), N.ptr(gslice), n, N.BF_REG_L2, GATE_L2 if is_gate else KERNEL_L2, reg,
-                      N.ptr(total[1:2]), N.stream_ptr(w))
-        for buf, off, n in self._unaligned:                            # staged gradients of tensors at unaligned offsets (a copy)
-            grads[off:off + n].copy_(buf)
-        _call("bf_op_axpy", N.ptr(total[2:3]), N.ptr(total[1:2]), reg, 0, 1, N.stream_ptr(total))
-        _call("bf_op_axpy", N.ptr(total), N.ptr(total[2:3]), 1.0, 0, 1, N.stream_ptr(total))
-        self.totals = total
+                call("bf_op_reg_elementwise", N.ptr(w), N.ptr(gslice), n, N.BF_REG_L2, GATE_L2 if is_gate else KERNEL_L2, reg,
+                     N.ptr(total[1:2]), N.stream_ptr(w))
+        self._finish(total, reg)
         return preds, scale_losses, total
-
-    def _grad_view(self, name, grads):
-        off, shape, _ = self.off[name]
-        n = int(np.prod(shape))
-        for buf, o, nn in self._unaligned:
-            if o == off:
-                return buf
-        return grads[off:off + n]
