@@ -29,6 +29,8 @@ from .pyramid import (build_pyramid_model, build_inverse_pyramid_model, multisca
 from .dataset import dataset_builder, PrepareData, noise_augment
 from .export_model import export_model
 from .file_operations import load_image
+from . import metrics
+from .metrics import ImageMetrics, image_metrics, image_metric_sums, psnr, ssim, mae, evaluate
 from . import regularizers
 from .custom_layers import RandomOnOff, Multiplier, ChannelwiseMultiplier
 

@@ -17,6 +17,7 @@ BF_OK, BF_EINVAL, BF_EUNSUPPORTED, BF_EWORKSPACE, BF_EHIP = 0, -1, -2, -3, -4
 BF_ACT_LINEAR, BF_ACT_RELU, BF_ACT_LEAKY_RELU = 0, 1, 2
 BF_REG_NONE, BF_REG_L1, BF_REG_L2 = 0, 1, 2
 BF_MODE_INFERENCE, BF_MODE_TRAIN = 0, 1
+BF_DTYPE_U8, BF_DTYPE_F32 = 0, 1
 BF_LOSS_COUNT = 8
 (BF_LOSS_TOTAL, BF_LOSS_DENOISER_TOTAL, BF_LOSS_MAE, BF_LOSS_MSE, BF_LOSS_SSIM,
  BF_LOSS_REGULARIZATION, BF_LOSS_MODEL_TOTAL, BF_LOSS_GRAD_NORM) = range(8)
@@ -42,7 +43,7 @@ class TensorInfo(C.Structure):
                 ("shape", C.c_int32 * 4), ("kind", C.c_int32), ("regularizer", C.c_int32)]
 
 
-_P, _I, _I64, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_P, _I, _I64, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); exactly the declarations of include/bfcnn_hip.h
 SIGNATURES = {
@@ -69,6 +70,8 @@ SIGNATURES = {
     "bf_laplacian_split": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bf_strided_slice2": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "bf_noise_augment": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, C.c_uint64, _P]),
+    "bf_image_metrics_scratch_bytes": (_I64, [_I, _I, _I, _I, _I]),
+    "bf_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _D, _D, _D, _P, _P, _I64, _P]),
     "bf_op_pack_pointwise": (_I, [_P, _P, _I, _I, _P]),
     "bf_op_pointwise": (_I, [_P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _F, _P]),
     "bf_op_pointwise_ex": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _F, _I, _P]),

@@ -1,0 +1,182 @@
+// Image-quality sums of two NHWC batches (uint8 or float32) in one pass: per image the sum of squared differences, the sum
+// of absolute differences and the sum of the SSIM map of tf.image.ssim (TF 2.13 _ssim_per_channel / _ssim_helper; the formula
+// is written out at the top of loss_terms.hip) over all VALID windows and channels.  The host forms mse, mae, psnr and ssim
+// from them (blind_image_denoising_amd/metrics.py).  Unlike ssim_fwd_kernel this is not tied to a training step: any window
+// size 3..11, any H, W >= the window, C in 1..4, no gradient maps.
+//
+// Layout.  The window is separable (softmax over the grid of -(i^2 + j^2) / (2 sigma^2) = outer product of the normalised
+// 1-D Gaussian), and the channels of a row are interleaved, so a row is treated as W*C elements and the horizontal taps of
+// element e are e + k*C.  A workgroup (4 waves) owns a tile of 16 window rows x 64 window elements (one element per lane):
+//   1. stage the tile of both images with its (F-1) row / (F-1)*C element halo in LDS as fp32 (a uint8 is exact in fp32),
+//      at most 26 x 104 elements each; the squared / absolute differences of the elements the tile owns ride in this pass;
+//   2. row pass: per staged row and lane the four moments g*x, g*y, g*(x y), g*(x^2 + y^2) over the F horizontal taps -> LDS;
+//   3. column pass: the F vertical taps over those, then S, summed per lane;
+//   4. wave shuffle + LDS reduction in a fixed order -> one partial triple per workgroup in scratch.
+// A second launch (one workgroup per image) adds the partials of an image in a fixed order: two calls on the same input
+// return the same bits; there are no atomics.  All lanes of a wave read consecutive LDS words: no bank conflicts.
+//
+// Numerics.  q - a^2 - b^2 cancels five digits, so the moments and S are carried in fp64 (fp64 FMA is half the fp32 rate on
+// gfx950 and the kernel has 8 F multiply-adds per window: cheap next to any denoiser forward).  uint8 differences are
+// accumulated as integers per thread and as fp64 from there on (integers below 2^53: exact in any order).
+#include "bf_common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int IM_MAXF = 11, IM_MAXC = 4;
+constexpr int IM_TH = 16;                                   // window rows of a tile (4 per wave in the column pass)
+constexpr int IM_TE = 64;                                   // window elements (pixel x channel) of a tile row: one per lane
+constexpr int IM_SR = IM_TH + IM_MAXF - 1;                  // staged rows
+constexpr int IM_SE = IM_TE + (IM_MAXF - 1) * IM_MAXC;      // staged elements per row
+
+struct ImWindow { double g[IM_MAXF]; };
+
+struct ImTiles {
+    int x, y;
+    ImTiles(int H, int W, int C, int F) : x(((W - F + 1) * C + IM_TE - 1) / IM_TE), y((H - F + 1 + IM_TH - 1) / IM_TH) {}
+    int64_t per_image() const { return (int64_t)x * y; }
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void image_metrics_tile_kernel(const T* __restrict__ a, const T* __restrict__ b, ImWindow win,
+                                                                 int H, int W, int C, int F, int tiles_x, int tiles_y,
+                                                                 double c1, double c2, double* __restrict__ partial)
+{
+    __shared__ float xs[IM_SR][IM_SE], ys[IM_SR][IM_SE];
+    __shared__ double mom[4][IM_SR][IM_TE];
+    __shared__ double red[4][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int t = blockIdx.x;
+    const int tx = t % tiles_x;
+    t /= tiles_x;
+    const int ty = t % tiles_y, img = t / tiles_y;
+    const int WC = W * C, e0 = tx * IM_TE, y0 = ty * IM_TH;
+    const int ne = min(IM_TE, (W - F + 1) * C - e0), nr = min(IM_TH, H - F + 1 - y0);      // the windows of this tile
+    const int se = ne + (F - 1) * C, sr = nr + F - 1;            // what they read: e0 + se <= W*C, y0 + sr <= H
+    // the elements whose differences this tile adds: its own 16 x 64, the last tile of a row / column up to the image's edge
+    const int own_e = tx == tiles_x - 1 ? se : IM_TE, own_r = ty == tiles_y - 1 ? sr : IM_TH;
+
+    double ssd = 0.0, sad = 0.0;
+    unsigned issd = 0u, isad = 0u;                                // uint8: at most 14 elements per thread, 65025 each
+    for (int r = wave; r < sr; r += 4) {
+        const int64_t row = ((int64_t)img * H + y0 + r) * WC + e0;
+        for (int e = lane; e < se; e += 64) {
+            const T x = a[row + e], y = b[row + e];
+            xs[r][e] = (float)x;
+            ys[r][e] = (float)y;
+            if (r < own_r && e < own_e) {
+                if constexpr (sizeof(T) == 1) {
+                    const int d = (int)x - (int)y;
+                    issd += (unsigned)(d * d);
+                    isad += (unsigned)abs(d);
+                } else {
+                    const double d = (double)x - (double)y;
+                    ssd += d * d;
+                    sad += fabs(d);
+                }
+            }
+        }
+    }
+    if constexpr (sizeof(T) == 1) { ssd = (double)issd; sad = (double)isad; }
+    __syncthreads();
+
+    if (lane < ne)
+        for (int r = wave; r < sr; r += 4) {
+            double ma = 0.0, mb = 0.0, ms = 0.0, mq = 0.0;
+            for (int k = 0; k < F; ++k) {
+                const double g = win.g[k], x = xs[r][lane + k * C], y = ys[r][lane + k * C];
+                ma += g * x; mb += g * y; ms += g * (x * y); mq += g * (x * x + y * y);
+            }
+            mom[0][r][lane] = ma; mom[1][r][lane] = mb; mom[2][r][lane] = ms; mom[3][r][lane] = mq;
+        }
+    __syncthreads();
+
+    double ssim = 0.0;
+    if (lane < ne)
+        for (int r = wave * (IM_TH / 4); r < min(nr, (wave + 1) * (IM_TH / 4)); ++r) {
+            double ma = 0.0, mb = 0.0, ms = 0.0, mq = 0.0;
+            for (int k = 0; k < F; ++k) {
+                const double g = win.g[k];
+                ma += g * mom[0][r + k][lane]; mb += g * mom[1][r + k][lane];
+                ms += g * mom[2][r + k][lane]; mq += g * mom[3][r + k][lane];
+            }
+            const double nl = 2.0 * ma * mb + c1, dl = ma * ma + mb * mb + c1;
+            const double nc = 2.0 * ms - 2.0 * ma * mb + c2, dc = mq - ma * ma - mb * mb + c2;
+            ssim += (nl / dl) * (nc / dc);
+        }
+
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        ssd += __shfl_xor(ssd, m); sad += __shfl_xor(sad, m); ssim += __shfl_xor(ssim, m);
+    }
+    if (lane == 0) { red[wave][0] = ssd; red[wave][1] = sad; red[wave][2] = ssim; }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        partial[(int64_t)blockIdx.x * 3 + threadIdx.x] =
+            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// out[img] = {sum of squared differences, sum of absolute differences, sum of S, number of S terms}; one workgroup per image
+__global__ __launch_bounds__(256) void image_metrics_finalize_kernel(const double* __restrict__ partial, int64_t tiles, double terms,
+                                                                     double* __restrict__ out)
+{
+    __shared__ double red[3][256];
+    const double* p = partial + (int64_t)blockIdx.x * tiles * 3;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = threadIdx.x; i < tiles; i += 256)
+        for (int j = 0; j < 3; ++j) acc[j] += p[i * 3 + j];
+    for (int j = 0; j < 3; ++j) red[j][threadIdx.x] = acc[j];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st)
+            for (int j = 0; j < 3; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) out[(int64_t)blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
+    if (threadIdx.x == 3) out[(int64_t)blockIdx.x * 4 + 3] = terms;
+}
+
+bool im_shape_ok(int B, int H, int W, int C, int F)
+{
+    if (B <= 0 || C < 1 || C > IM_MAXC || F < 3 || F > IM_MAXF || !(F & 1) || H < F || W < F) return false;
+    return (int64_t)W * C <= INT32_MAX - IM_SE && ImTiles(H, W, C, F).per_image() * B <= INT32_MAX;
+}
+
+}  // namespace
+
+extern "C" int64_t bf_image_metrics_scratch_bytes(int B, int H, int W, int C, int F)
+{
+    if (!im_shape_ok(B, H, W, C, F)) return BF_EINVAL;
+    return ImTiles(H, W, C, F).per_image() * B * 3 * (int64_t)sizeof(double);
+}
+
+extern "C" int bf_image_metrics(const void* a, const void* b, int dtype, int B, int H, int W, int C, double max_val, int F,
+                                double filter_sigma, double k1, double k2, double* out, void* scratch, int64_t scratch_bytes,
+                                void* stream)
+{
+    if (!a || !b || !out || !scratch || (dtype != BF_DTYPE_U8 && dtype != BF_DTYPE_F32) || !im_shape_ok(B, H, W, C, F)) return BF_EINVAL;
+    if (!(max_val > 0.0) || !(filter_sigma > 0.0) || !(k1 >= 0.0) || !(k2 >= 0.0)) return BF_EINVAL;
+    if (scratch_bytes < bf_image_metrics_scratch_bytes(B, H, W, C, F) || ((uintptr_t)scratch | (uintptr_t)out) % 8) return BF_EINVAL;
+    if (dtype == BF_DTYPE_F32 && ((uintptr_t)a | (uintptr_t)b) % 4) return BF_EINVAL;
+    ImWindow win;
+    double sum = 0.0;
+    for (int i = 0; i < F; ++i) {
+        const double c = i - (F - 1) / 2.0;
+        win.g[i] = exp(-0.5 * c * c / (filter_sigma * filter_sigma));
+        sum += win.g[i];
+    }
+    for (int i = 0; i < IM_MAXF; ++i) win.g[i] = i < F ? win.g[i] / sum : 0.0;
+    const ImTiles tiles(H, W, C, F);
+    const double c1 = (k1 * max_val) * (k1 * max_val), c2 = (k2 * max_val) * (k2 * max_val);
+    double* partial = (double*)scratch;
+    const dim3 grid((unsigned)(tiles.per_image() * B));
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == BF_DTYPE_U8)
+        hipLaunchKernelGGL(image_metrics_tile_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)a, (const uint8_t*)b, win, H, W, C, F,
+                           tiles.x, tiles.y, c1, c2, partial);
+    else
+        hipLaunchKernelGGL(image_metrics_tile_kernel<float>, grid, dim3(256), 0, s, (const float*)a, (const float*)b, win, H, W, C, F,
+                           tiles.x, tiles.y, c1, c2, partial);
+    hipLaunchKernelGGL(image_metrics_finalize_kernel, dim3(B), dim3(256), 0, s, partial, tiles.per_image(), (double)(H - F + 1) * (W - F + 1) * C, out);
+    return hipGetLastError() == hipSuccess ? BF_OK : BF_EHIP;
+}

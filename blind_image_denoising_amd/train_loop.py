@@ -337,23 +337,28 @@ class DataParallelTrainer:
 # ---- outer loop --------------------------------------------------------------------------------
 
 def train_loop(pipeline_config_path, checkpoint_directory: str = None, weights_dir: str = None, dataset: Iterable = None,
-               device=None, max_steps: Optional[int] = None, model_dir: str = None):
+               device=None, max_steps: Optional[int] = None, model_dir: str = None, evaluation_batches: Iterable = None):
     """bfcnn/train_loop.py:40-601 with the reference's positional order (pipeline_config_path, checkpoint_directory, weights_dir);
-    `model_dir` is this package's older keyword for the same directory.  Returns (model, loss history).  See `_train_loop`."""
+    `model_dir` is this package's older keyword for the same directory.  Returns (model, loss history).  `evaluation_batches`:
+    clean uint8 batches for the `train.evaluation` section instead of its `inputs` directories.  See `_train_loop`."""
     model_dir = checkpoint_directory if checkpoint_directory is not None else model_dir
     if model_dir is None:
         raise ValueError("checkpoint_directory must be given")
-    return _train_loop(pipeline_config_path, str(model_dir), dataset, None if weights_dir is None else str(weights_dir), device, max_steps)
+    return _train_loop(pipeline_config_path, str(model_dir), dataset, None if weights_dir is None else str(weights_dir), device, max_steps,
+                       evaluation_batches)
 
 
 def _train_loop(pipeline_config_path, model_dir: str, dataset: Iterable = None, weights_dir: str = None,
-                device=None, max_steps: Optional[int] = None):
+                device=None, max_steps: Optional[int] = None, evaluation_batches: Iterable = None):
     """Outer loop of bfcnn/train_loop.py:40-601 reduced to what surrounds the hot path: config ->
     loss / optimizer / model builders -> checkpoint manager (restore the latest checkpoint of `model_dir` if there is one:
     weights, BN statistics, Adam slots, step, epoch -- train_loop.py:158-181) -> epochs over `dataset` (an iterable
     yielding (input_image_batch, noisy_image_batch) float tensors in value range) with gradient accumulation over
     `gpu_batches_per_step` micro-batches; `dataset=None`: the configuration's own `dataset` section, image directories and all), a checkpoint every `checkpoint_every` steps and at the end of every epoch
     (train_loop.py:563-566, 597) -> model directory per epoch.
+    With a `train.evaluation` section (metrics.parse_evaluation_config) the current weights are validated as the reference's loop
+    does when it writes summaries (train_loop.py:507-530), with numbers instead of images: every `every` optimizer steps, or at the
+    end of each epoch, one record of metrics.evaluate goes to <model_dir>/evaluation.jsonl and to `model.evaluation_history`.
     The tf.data pipeline, TensorBoard summaries and TF's checkpoint format are out of scope."""
     from .checkpoint import Checkpoint, CheckpointManager
     config = load_config(pipeline_config_path)
@@ -384,6 +389,9 @@ def _train_loop(pipeline_config_path, model_dir: str, dataset: Iterable = None, 
         w = load_hydra(weights_dir, device=device).get_weights()
         model.set_weights(*w) if isinstance(w, tuple) else model.set_weights(w)
     fns = build_train_functions(model, loss_fn_map)
+    from .metrics import build_evaluator
+    evaluator = build_evaluator(train_config, model, model_dir, config.get(DATASET_STR), evaluation_batches)
+    model.evaluation_history = evaluator.history if evaluator is not None else []
     # per-output loss weights over the course of training (bfcnn/train_loop.py:350-381, optimizer.py:21-78)
     no_outputs = int(getattr(model, "depth", 1)) if getattr(model, "multi_output", False) else 1
     deep_supervision_schedule = deep_supervision_schedule_builder(
@@ -417,10 +425,14 @@ def _train_loop(pipeline_config_path, model_dir: str, dataset: Iterable = None, 
                 if checkpoint_every > 0 and ckpt.step > 0 and ckpt.step % checkpoint_every == 0:
                     manager.save()
                 ckpt.step += 1
+                if evaluator is not None and evaluator.due(ckpt.step):
+                    evaluator.run(ckpt.step, ckpt.epoch)
                 if (0 < total_steps <= ckpt.step) or (max_steps is not None and len(history) >= max_steps):
                     finished = True
                     break
         logger.info(f"end of epoch [{ckpt.epoch}], step {ckpt.step}, took [{time.time() - t0:.1f}] seconds")
+        if evaluator is not None and evaluator.config.every <= 0:
+            evaluator.run(ckpt.step, ckpt.epoch)
         save_model(model, os.path.join(model_dir, f"epoch_{ckpt.epoch}"), config)
         if not finished:
             ckpt.epoch += 1

@@ -211,6 +211,24 @@ int bf_strided_slice2(const float* in, float* out, int batch, int height, int wi
 int bf_noise_augment(const float* in, float* out_clean, float* out_noisy, int batch, int height, int width, int channels,
                      int flip_mask, float mult_std, float add_std, uint64_t seed, void* stream);
 
+/* Image-quality sums of two device batches a, b [batch,height,width,channels] (NHWC, both uint8 or both float32: `dtype`), what
+ * tf.image.psnr / tf.image.ssim and a mean absolute error are formed from (the acceptance check of the reference's
+ * tests/bfcnn/test_pretrained.py:62-78; blind_image_denoising_amd/metrics.py is the host side).  out = device double[batch][4]:
+ *   out[i][0] = sum (a - b)^2, out[i][1] = sum |a - b| over image i (uint8 inputs: exact integers),
+ *   out[i][2] = sum over all VALID windows and channels of the SSIM map of TF 2.13's _ssim_per_channel (window = softmax over
+ *               the filter_size x filter_size grid of -(i^2 + j^2) / (2 filter_sigma^2), c1 = (k1 max_val)^2, c2 = (k2 max_val)^2),
+ *   out[i][3] = the number of those terms, (height - filter_size + 1) * (width - filter_size + 1) * channels,
+ * so mse = out[0] / (H W C), mae = out[1] / (H W C), psnr = 20 log10(max_val) - 10 log10(mse), ssim = out[2] / out[3].
+ * filter_size odd in 3..11, height and width >= filter_size, channels in 1..4; no padding and no float copy of the images.
+ * Sums are carried in fp64 and reduced in a fixed order (per-workgroup partials in `scratch`, then one workgroup per image):
+ * repeated calls return the same bits.  bf_image_metrics_scratch_bytes: the scratch one call needs (BF_EINVAL for a shape the
+ * call refuses); BF_EINVAL for NULL, a bad shape, dtype or window, or too little scratch. */
+enum bf_dtype { BF_DTYPE_U8 = 0, BF_DTYPE_F32 = 1 };
+int64_t bf_image_metrics_scratch_bytes(int batch, int height, int width, int channels, int filter_size);
+int bf_image_metrics(const void* a, const void* b, int dtype, int batch, int height, int width, int channels, double max_val,
+                     int filter_size, double filter_sigma, double k1, double k2, double* out, void* scratch, int64_t scratch_bytes,
+                     void* stream);
+
 /* ---- unet_laplacian backbone operators (BASELINE.json configs[4]) ------------------------------
  * What bfcnn/backbone_unet_laplacian.py:281-606 builds from keras layers, as fp32 NHWC device operators; the host
  * (blind_image_denoising_amd/unet_laplacian.py) chains them as the reference builder chains its layers.
