@@ -133,24 +133,20 @@ struct FusedBlockArgs {
     int B, H, W;
     int tiles_x, tiles_y, ntiles;
     int act1_relu;        // activation of conv1 (1 = relu, 0 = linear)
-    const float* zeros;   // >= 64 B of zeros, 16-B aligned (source of out-of-image elements for the LDS-DMA variant)
-    unsigned long long* dbg;  // diagnostic builds only (per-wave phase cycle sums), else NULL
+    const float* zeros;   // >= 64 B of zeros, 16-B aligned (source of out-of-image elements of the tile DMA)
 };
 
 // split-f16 ("f16x3") fused block on the f16 matrix cores (fused_h3.hip).  Activations are "split-planar":
 // per image 4 planes [H][W][8 x f16] = hi(c0..7), hi(c8..15), lo(c0..7), lo(c8..15), value = hi + lo.
-#define BF_H3_WPACK_FLOATS (10 * 64 * 4)                      // ten A-operand register images of 16 B per lane
-#define BF_H3R_WPACK_FLOATS (13 * 64 * 4)                     // row-streaming kernel: 12 A-operand images + s2 * identity
-// per block: w1, w2 (group kernel), aux (1/s1 | scale/s2 | shift | pad), w1r, w2r (row-streaming kernel)
-#define BF_H3_BLOCK_FLOATS (2 * BF_H3_WPACK_FLOATS + 64 + 2 * BF_H3R_WPACK_FLOATS)
+#define BF_H3R_WPACK_FLOATS (13 * 64 * 4)                     // one convolution: 12 A-operand register images of 16 B per lane + s2 * identity
+// per block (pack_h3.hip): aux (1/s1 | - | shift | 1/s2), w1r, w2r
+#define BF_H3_BLOCK_FLOATS (64 + 2 * BF_H3R_WPACK_FLOATS)
 struct FusedH3Args {
     const void* in;       // split-planar block input x
     void* out;            // split-planar x + scale*conv2(act(conv1 x)) + shift
-    const void* w1;       // [10][64] x 16 B
-    const void* w2;
-    const void* w1r;      // [13][64] x 16 B (row-streaming kernel)
-    const void* w2r;
-    const float* aux;     // [0..15] 1/s1, [16..31] scale/s2 (group kernel), [32..47] shift, [48..63] 1/s2r (row kernel)
+    const void* w1r;      // [13][64] x 16 B: block + 64 floats
+    const void* w2r;      //                  block + 64 + BF_H3R_WPACK_FLOATS
+    const float* aux;     // block + 0: [0..15] 1/s1, [32..47] shift, [48..63] 1/s2
     int B, H, W;
     int tiles_x, tiles_y, ntiles;   // filled in by the launcher
     int rows_per_tile;    // full-row streaming kernel (fused_h3v.hip): rows per band, filled in by the launcher
@@ -177,7 +173,7 @@ bool       bf_fused_block_h3_use_pairs(const FusedH3Args& a);   // two blocks pe
 const char* bf_fused_block_h3_kernel_name(const FusedH3Args& a);
 const char* bf_fused_block_kernel_name();                      // conv3x3_c16.hip: the exact-fp32 fused block
 // library default of FusedH3Args::variant (handle-less debug entries): 4 = full-row streaming kernel where it applies
-// (W <= 256), 1 = row-streaming tile kernel, 0 / 2 / 3 = earlier tile kernels (A/B only)
+// (W <= 256), 2 = row-streaming tile kernel on 16 x 16 tiles, every other value (1; 0 and 3 of retired kernels) = on 16 x 32 tiles
 void       bf_set_h3_variant(int v);
 hipError_t bf_launch_fused_block_h3v(const FusedH3Args& a, hipStream_t s);      // fused_h3v.hip
 bool       bf_fused_block_h3v_supports(int H, int W);
@@ -331,7 +327,7 @@ hipError_t bf_launch_h3_to_f32(const void* y, float* x, int B, int H, int W, hip
 hipError_t bf_launch_conv3x3_c16(const ConvArgs& a, int epi, hipStream_t s);
 int        bf_conv3x3_c16_grid(int B, int H, int W);
 hipError_t bf_launch_fused_block(const FusedBlockArgs& a, hipStream_t s);
-void       bf_set_fused_tile(int variant);   // A/B of tile geometries (process-wide, tools/ only)
+void       bf_set_fused_tile(int variant);   // kept for bf_set_option("fused_tile"): every value runs fused_block_v4_kernel
 hipError_t bf_launch_pack_conv(const float* w_hwio, float* wpack, int transpose_flip, hipStream_t s);
 hipError_t bf_launch_wgrad3x3_c16(const float* x, const float* dy, float* partial, float* dw,
                                   int B, int H, int W, hipStream_t s);

@@ -525,7 +525,7 @@ static int forward_common(bf_handle h, const float* pk, const void* in, int in_i
             memset(&fa, 0, sizeof(fa));
             fa.in = buf[cur]; fa.out = buf[cur ^ 1];
             for (int b = 0; b < 2; ++b) {
-                const float* aux = pk + h->k_h3 + (int64_t)(i + b) * BF_H3_BLOCK_FLOATS + 2 * BF_H3_WPACK_FLOATS;
+                const float* aux = pk + h->k_h3 + (int64_t)(i + b) * BF_H3_BLOCK_FLOATS;
                 fa.aux[b] = aux; fa.w1r[b] = aux + 64; fa.w2r[b] = aux + 64 + BF_H3R_WPACK_FLOATS;
             }
             fa.B = B; fa.H = H; fa.W = W;
@@ -565,10 +565,9 @@ static int forward_common(bf_handle h, const float* pk, const void* in, int in_i
             }
             cur = src;
         } else if (h3) {
-            const float* b3 = pk + h->k_h3 + (int64_t)i * BF_H3_BLOCK_FLOATS;
             FusedH3Args fa;
             fa.in = buf[cur]; fa.out = buf[cur ^ 1];
-            fa.w1 = b3; fa.w2 = b3 + BF_H3_WPACK_FLOATS; fa.aux = b3 + 2 * BF_H3_WPACK_FLOATS;
+            fa.aux = pk + h->k_h3 + (int64_t)i * BF_H3_BLOCK_FLOATS;
             fa.w1r = fa.aux + 64; fa.w2r = fa.aux + 64 + BF_H3R_WPACK_FLOATS;
             fa.B = B; fa.H = H; fa.W = W; fa.tiles_x = fa.tiles_y = fa.ntiles = 0; fa.rows_per_tile = 0; fa.variant = h->h3_variant;
             // consecutive blocks walk the batch in opposite directions: a block starts on the bands the previous one wrote
@@ -591,7 +590,7 @@ static int forward_common(bf_handle h, const float* pk, const void* in, int in_i
             fa.w1pack = blk; fa.w2pack = blk + BF_WPACK_FLOATS;
             fa.scale = blk + 2 * BF_WPACK_FLOATS; fa.shift = fa.scale + 16;
             fa.B = B; fa.H = H; fa.W = W; fa.tiles_x = fa.tiles_y = fa.ntiles = 0;
-            fa.act1_relu = d.activation == BF_ACT_RELU; fa.dbg = nullptr; fa.zeros = pk + h->k_zero;
+            fa.act1_relu = d.activation == BF_ACT_RELU; fa.zeros = pk + h->k_zero;
             BF_HIP(bf_launch_fused_block(fa, s), "fused_block");
             ran(bf_fused_block_kernel_name(), 1);
             cur ^= 1;
@@ -1390,7 +1389,7 @@ extern "C" int bf_debug_conv3x3(const float* in, const float* w_hwio, float* out
 }
 
 static unsigned long long* g_fused_dbg = nullptr;
-// diagnostic builds (tools/ablate.sh 8): device buffer of 512*8*8 u64 that receives per-wave phase cycle sums
+// diagnostic builds (H3_ABLATE=32, tools/stamp_h3.py and its siblings): device buffer of 512*8*8 u64 that receives per-wave phase cycle sums
 extern "C" int bf_debug_set_fused_dbg(void* buf) { g_fused_dbg = (unsigned long long*)buf; return BF_OK; }
 
 extern "C" int bf_debug_conv3x3_grid(int B, int H, int W) { return bf_conv3x3_c16_grid(B, H, W); }
@@ -1407,7 +1406,6 @@ extern "C" int bf_debug_fused_block(const float* in, const float* w1_hwio, const
     fa.zeros = wpack_scratch + 2 * BF_WPACK_FLOATS;
     fa.in = in; fa.out = out; fa.w1pack = wpack_scratch; fa.w2pack = wpack_scratch + BF_WPACK_FLOATS; fa.scale = scale;
     fa.shift = shift; fa.B = B; fa.H = H; fa.W = W; fa.tiles_x = fa.tiles_y = fa.ntiles = 0; fa.act1_relu = act1_relu;
-    fa.dbg = g_fused_dbg;
     return bf_launch_fused_block(fa, s) == hipSuccess ? BF_OK : BF_EHIP;
 }
 
@@ -1439,7 +1437,7 @@ extern "C" int bf_debug_fused_block_h3(const float* in, const float* w1_hwio, co
     if (bf_launch_pack_h3(params, state, 0, 4608 + 16, pk, BF_H3_BLOCK_FLOATS, 1, 0, 0.f, scale, shift, s) != hipSuccess) return BF_EHIP;
     if (bf_launch_h3_from_f32(in, xa, B, H, W, s) != hipSuccess) return BF_EHIP;
     FusedH3Args fa;
-    fa.in = xa; fa.out = ya; fa.w1 = pk; fa.w2 = pk + BF_H3_WPACK_FLOATS; fa.aux = pk + 2 * BF_H3_WPACK_FLOATS;
+    fa.in = xa; fa.out = ya; fa.aux = pk;
     fa.w1r = fa.aux + 64; fa.w2r = fa.aux + 64 + BF_H3R_WPACK_FLOATS;
     fa.B = B; fa.H = H; fa.W = W; fa.tiles_x = fa.tiles_y = fa.ntiles = 0; fa.rows_per_tile = 0; fa.variant = -1; fa.reverse_tiles = 0; fa.act1_relu = act1_relu;
     fa.zeros = zeros; fa.dump = dump; fa.dbg = g_fused_dbg;
@@ -1479,7 +1477,7 @@ extern "C" int bf_debug_fused_block2_h3(const float* in, const float* w_hwio, co
     memset(&fa, 0, sizeof(fa));
     fa.in = xa; fa.out = ya;
     for (int b = 0; b < 2; ++b) {
-        const float* aux = pk + b * BF_H3_BLOCK_FLOATS + 2 * BF_H3_WPACK_FLOATS;
+        const float* aux = pk + b * BF_H3_BLOCK_FLOATS;
         fa.aux[b] = aux; fa.w1r[b] = aux + 64; fa.w2r[b] = aux + 64 + BF_H3R_WPACK_FLOATS;
     }
     fa.B = B; fa.H = H; fa.W = W; fa.reverse_tiles = reverse ? 1 : 0; fa.act1_relu = act1_relu;

@@ -1,5 +1,5 @@
-// Device helpers shared by the split-f16 ("f16x3") kernels: fused_h3.hip (tile kernels, training convolutions) and
-// fused_h3v.hip (row-streaming full-width kernel).  Arithmetic and layout: see the header of fused_h3.hip.
+// Device helpers shared by the split-f16 ("f16x3") kernels: fused_h3.hip (tile kernel), train_conv_h3.hip (training
+// convolutions) and fused_h3v.hip (row-streaming full-width kernel).  Arithmetic and layout: see the header of fused_h3.hip.
 #pragma once
 #include "bf_common.h"
 
@@ -76,7 +76,7 @@ __device__ __forceinline__ void h3_split(const f32x4 v, h4& hi, h4& lo)
 
 // NOTE on `interior` shortcuts in the conv2 epilogues: `if (!interior && out_of_image) p = dump` made hipcc branch over the
 // select on the uniform `interior`, and on the taken path its hazard recognizer left ONE wait state between the last
-// MFMA of a row and the v_pk_fma that reads the accumulator: stale .zw halves on interior tiles of the wave-specialised
+// MFMA of a row and the v_pk_fma that reads the accumulator: stale .zw halves on interior tiles of the (since retired) wave-specialised
 // kernel (caught by the parity tests).  The out-of-image select is therefore unconditional (per-lane condition, no branch).
 //
 // hi / lo of the lane's four channels, then a row exchange (v_permlane16_swap_b32: result 0 = [a.row0, b.row0, a.row2,

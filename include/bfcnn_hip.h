@@ -597,7 +597,10 @@ int bf_op_axpy(float* y, const float* x, float a, int overwrite, int64_t n, void
  *   kernel); 0 (default; the two measure the same).  "h3_pair" = 2 and "base_rows" = 2 (A/B and tests only) run the two-block kernel /
  *   the row-streaming base convolution wherever they CAN run instead of where the selection prefers them ("base_rows" = 0: the
  *   tile kernel of the base convolution everywhere; process-wide).
- * "fused_tile" / "h3_variant": kernel variants of the fused blocks (A/B only; negative = default). */
+ * "h3_variant": kernel of the split-f16 fused blocks (A/B only; negative = default): 4 full-row streaming where it applies,
+ *   2 row-streaming 16x16 tiles, every other value (1; 0 and 3 named kernels that have been retired) row-streaming 16x32 tiles.
+ * "fused_tile": accepted for compatibility; every value runs the one exact-fp32 fused block kernel (fused_block_v4_kernel).
+ *   Both succeed for every integer. */
 int bf_set_option(bf_handle h, const char* key, int value);
 
 /* with option "timing" = 1 every forward brackets its residual-block launches with two HIP events on

@@ -30,7 +30,9 @@ int64_t bf_debug_fused_block2_h3_scratch_floats(int batch, int height, int width
 int bf_debug_fused_block2_h3(const float* in, const float* w_hwio, const float* scale, const float* shift, float* out,
                              float* scratch, int batch, int height, int width, int act1_relu, int reverse, void* stream);
 /* kernel the handle-less entry above launches (a handle's own choice is bf_set_option "h3_variant"): 4 full-row streaming
-   (falls back to 1 beyond 256 columns), 1 row-streaming tiles, 0 / 2 / 3 earlier tile kernels; < 0 = library default */
+   (falls back to 1 beyond 256 columns), 2 row-streaming 16x16 tiles, 1 row-streaming 16x32 tiles; < 0 = library default.
+   Succeeds for every integer: any other value (0 and 3 were kernels that have been retired) runs what 1 runs; + 256 walks
+   the bands of the full-row kernel bottom-up */
 int bf_debug_set_h3_variant(int variant);
 int64_t bf_debug_conv3x3_h3_scratch_floats(void);
 int bf_debug_conv3x3_h3(const float* in, const float* w_hwio, float* out, const float* res, const float* mask, float* stats,

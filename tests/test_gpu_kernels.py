@@ -122,7 +122,8 @@ def test_conv3x3_h3_epilogues_and_stats(shape):
 
 @pytest.fixture(params=[0, 1, 2, 3, 4], ids=["tile14x32x4", "tile32x32x8", "tile16x64x8", "dma14x32x4", "v4_14x32x4"])
 def fused_tile(request):
-    """every fused-block tile geometry compiled into the library must pass the same parity tests."""
+    """every value of "fused_tile" must pass the same parity tests: 4 is the kernel the library keeps, 0-3 name retired tile
+    geometries and run it too."""
     import blind_image_denoising_amd as bf
     m = bf.model_builder(O.canonical_config(no_layers=0)["model"], device="cuda").hydra
     m.set_option("fused_tile", request.param)
@@ -164,7 +165,8 @@ def test_fused_block_many_tiles_persistent_schedule(fused_tile):
 # ---- split-f16 ("f16x3") fused block: same oracle, same bar as the exact-fp32 kernels ---------------------
 @pytest.fixture(params=[4, 260, 1, 0, 2, 3], ids=["fullrow", "fullrow_up", "rows", "groups", "rows16x16", "specialised"], autouse=False)
 def h3_variant(request):
-    """every split-f16 kernel (full-row streaming, row-streaming tiles, group-per-pass, ...) must pass the same parity tests."""
+    """every split-f16 selection (full-row streaming top-down and bottom-up, row-streaming 16x32 and 16x16 tiles) must pass the same
+    parity tests; 0 "groups" and 3 "specialised" name retired kernels and run the 16x32 row-streaming tile kernel."""
     N.lib().bf_debug_set_h3_variant(request.param)
     yield request.param
     N.lib().bf_debug_set_h3_variant(-1)
@@ -226,6 +228,33 @@ def test_fused_block_h3_many_tiles_persistent_schedule(h3_variant):
     sub = slice(1, 2)
     t64 = np.maximum(O.conv2d_same(x[sub].astype(np.float64), w1.astype(np.float64)), 0)
     assert_close(got[sub], x[sub] + O.conv2d_same(t64, w2.astype(np.float64)), what="h3 vs oracle")
+
+
+@pytest.mark.parametrize("shape", [(1, 17, 33), (2, 33, 65)])       # an edge tile in both directions; several images
+def test_retired_variant_numbers_fall_back_to_the_kept_kernels(shape):
+    """the numbers of retired kernels and unknown ones are still accepted: "h3_variant" 0, 3 and 7 run the 16x32 row-streaming
+    tile kernel (bitwise what 1 gives), every "fused_tile" runs the one exact-fp32 kernel (bitwise the default)."""
+    import blind_image_denoising_amd as bf
+    B, H, W = shape
+    x = _rand((B, H, W, 16), 15)
+    w1, w2 = _rand((3, 3, 16, 16), 16) * 0.1, _rand((3, 3, 16, 16), 17) * 0.1
+    sc, sh = _rand(16, 18), _rand(16, 19)
+    try:
+        assert N.lib().bf_debug_set_h3_variant(1) == N.BF_OK
+        rows = fused_block_h3_gpu(x, w1, w2, sc, sh, 1)
+        for v in (0, 3, 7):
+            assert N.lib().bf_debug_set_h3_variant(v) == N.BF_OK
+            assert np.array_equal(fused_block_h3_gpu(x, w1, w2, sc, sh, 1), rows), f"h3_variant {v}"
+    finally:
+        N.lib().bf_debug_set_h3_variant(-1)
+    m = bf.model_builder(O.canonical_config(no_layers=0)["model"], device="cuda").hydra
+    default = fused_block_gpu(x, w1, w2, sc, sh, 1)
+    try:
+        for v in range(4):
+            m.set_option("fused_tile", v)        # raises unless the library returns success
+            assert np.array_equal(fused_block_gpu(x, w1, w2, sc, sh, 1), default), f"fused_tile {v}"
+    finally:
+        m.set_option("fused_tile", -1)
 
 
 # ---- two blocks per launch on 128-column strips (fused_h3w.hip): same oracle, same bar -------------------------------------
