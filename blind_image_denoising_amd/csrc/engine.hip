@@ -45,7 +45,6 @@ struct bf_engine {
     int train_arith = 1;
     int train_zigzag = 1;           // split-f16 training: consecutive kernels walk their tiles in opposite directions
     int train_fused_fwd = 1;        // split-f16 training: BatchNorm apply + skip Add of block i formed while block i+1's first convolution stages its tile
-    int train_bwd_dbuf = 0;         // fused backward kernel: 512-thread form with double-buffered LDS images (A/B: 10 % slower)
     int train_fwd_block = 1;        // [3,3] blocks with BatchNorm + ReLU, W <= 256: the whole training forward of a block in ONE row-streaming
                                     // kernel (train_fwd_h3t.hip; T kept in LDS unless the backward pass reads it).  1 = where a forward holds
                                     // enough rows (bf_train_step), 2 = wherever it can run (tests), 0 = the two convolution kernels
@@ -55,8 +54,6 @@ struct bf_engine {
     int train_fold_finalize = 1;    // block kernels: the BatchNorm finalisation kernels between the blocks (bn_finalize / bn_bwd_finalize, ~6 us +
                                     // two kernel boundaries each, 34 per step of 1x18) run in the prologue of the next block kernel instead
     int train_fused_bwd = 1;        // split-f16 training: weight + data gradient (+ BatchNorm backward) of a convolution in one kernel
-    int train_fused_bwd2 = 0;       // [3,3] blocks with BatchNorm and ReLU: BOTH convolutions' backward in one kernel (bwd2_h3_kernel: 6 tensor
-                                    // passes for 9, but 348 us against 131 + 110: one workgroup per CU and a recomputed halo -- DESIGN 4.3)
     // optional HIP-event bracket around the residual-block launches of a forward (bench.py roofline)
     int timing = 0;
     // ring of event pairs: one pair per timed forward since the option was (re)set, BF_TIMING_RING forwards at most
@@ -222,11 +219,11 @@ extern "C" int bf_set_option(bf_handle h, const char* key, int value)
     if (!strcmp(key, "fused_head")) { h->fused_head = value ? 1 : 0; return BF_OK; }
     if (!strcmp(key, "train_zigzag")) { h->train_zigzag = value ? 1 : 0; return BF_OK; }
     if (!strcmp(key, "train_fused_fwd")) { h->train_fused_fwd = value ? 1 : 0; return BF_OK; }
-    if (!strcmp(key, "train_bwd_dbuf")) { h->train_bwd_dbuf = value ? 1 : 0; return BF_OK; }
     if (!strcmp(key, "train_fused_bwd")) { h->train_fused_bwd = value ? 1 : 0; return BF_OK; }
     if (!strcmp(key, "train_bwd_block")) { h->train_bwd_block = value < 0 ? 1 : (value > 2 ? 2 : value); return BF_OK; }
     if (!strcmp(key, "train_fwd_block")) { h->train_fwd_block = value < 0 ? 1 : (value > 2 ? 2 : value); return BF_OK; }
-    if (!strcmp(key, "train_fused_bwd2")) { h->train_fused_bwd2 = value ? 1 : 0; return BF_OK; }
+    // retired A/B options (their kernels lost and were removed): accepted and ignored
+    if (!strcmp(key, "train_fused_bwd2") || !strcmp(key, "train_bwd_dbuf")) return BF_OK;
     if (!strcmp(key, "train_fold_finalize")) { h->train_fold_finalize = value ? 1 : 0; return BF_OK; }
     if (!strcmp(key, "train_arith")) { h->train_arith = value < 0 ? 1 : (value ? 1 : 0); return BF_OK; }
     if (!strcmp(key, "arith")) { h->arith = value < 0 ? 1 : (value ? 1 : 0); return BF_OK; }
@@ -825,128 +822,154 @@ __global__ void fill_identity_affine_kernel(float* scale_shift)
     if (threadIdx.x < 16) { scale_shift[threadIdx.x] = 1.f; scale_shift[16 + threadIdx.x] = 0.f; }
 }
 
-extern "C" int bf_train_step(bf_handle h, const float* params, float* state, const float* gt, const float* noisy, int B, int H,
-                             int W, const bf_loss_desc* loss, float* predictions, float* grads, float* losses, void* ws,
-                             int64_t ws_bytes, void* stream)
-{
-    if (!h) return BF_EINVAL;
-    const bf_resnet_desc& d = h->d;
-    if (!params || !gt || !noisy || !loss || !grads || !losses || (h->n_state > 0 && !state))
-        return fail(h, BF_EINVAL, "bf_train_step: NULL argument");
-    if (loss->struct_size != (int32_t)sizeof(bf_loss_desc)) return fail(h, BF_EINVAL, "bf_loss_desc struct_size mismatch");
-    if (B <= 0 || H <= 0 || W <= 0) return fail(h, BF_EINVAL, "batch/height/width must be positive");
-    const bool extra_terms = loss->ssim_multiplier > 0.f || loss->mse_multiplier > 0.f;     // use_ssim / use_mse (loss.py:174-179)
-    if (loss->ssim_multiplier > 0.f && (H < 7 || W < 7)) return fail(h, BF_EINVAL, "SSIM needs images of at least 7x7");
-    if (loss->ssim_multiplier > 0.f && !d.denormalize)
-        return fail(h, BF_EUNSUPPORTED, "SSIM term (max_val 255) is built for the denormalised hydra output");
-    if (d.head_activation != BF_ACT_LINEAR) return fail(h, BF_EUNSUPPORTED, "training is built for the linear denoiser head");
-    if (d.block_convs < 1 || d.block_convs > 3) return fail(h, BF_EUNSUPPORTED, "training is built for blocks of 1 to 3 convolutions (got %d)", d.block_convs);
-    if (d.out_channels != d.in_channels) return fail(h, BF_EINVAL, "gt/prediction channel mismatch");
-    const TrainLayout L = train_layout(h, B, H, W);
-    if (!ws || (uintptr_t)ws % 16) return fail(h, BF_EWORKSPACE, "workspace must be a 16-byte aligned device buffer");
-    if (ws_bytes < L.total * 4) return fail(h, BF_EWORKSPACE, "workspace too small: %lld < %lld bytes", (long long)ws_bytes,
-                                            (long long)(L.total * 4));
-    hipStream_t s = (hipStream_t)stream;
-    float* w = (float*)ws;
-    const int N = d.no_layers;
-    const int nb = d.block_convs;                   // block: conv_0 [+ act] , conv_j + BN [+ act] (j >= 1), last one linear, + skip
-    const int unit = d.use_bn ? 2320 : 2304;        // floats from convolution kernel j >= 1 of a block to the next (gamma in between)
-    const int64_t npix = (int64_t)B * H * W;
-    const double count = (double)npix;
-    float* partial = w + L.partial;
-    double* stage1 = reinterpret_cast<double*>(w + L.stage1);     // (offset is a multiple of 2 floats: 8-byte aligned)
-    auto ACT = [&](int64_t i) { return w + L.acts + i * L.act_floats; };
-    // buffer map: A_i = ACT(i) (i = 0..N: block inputs / outputs) ; T(i,j) = input of convolution j >= 1 of block i (the
-    // activated output of convolution j-1) ; C(i,j) = raw output of convolution j >= 1 (in front of its BatchNorm) ; dA
-    auto A = [&](int i) { return ACT(i); };
-    auto T = [&](int i, int j) { return ACT(N + 1 + (int64_t)i * (nb - 1) + (j - 1)); };
-    auto C = [&](int i, int j) { return ACT(N + 1 + (int64_t)N * (nb - 1) + (int64_t)i * (nb - 1) + (j - 1)); };
-    float* dA = ACT(N + 1 + 2 * (int64_t)N * (nb - 1));
-    auto conv_off = [&](int j) { return j == 0 ? (int64_t)0 : 2304 + (int64_t)(j - 1) * unit; };     // inside a block's parameters
-    auto bn_idx = [&](int i, int j) { return (int64_t)i * (nb - 1) + (j - 1); };                       // BatchNorm of convolution j >= 1
+// What the three phases of a training step share: the problem, the workspace and its buffer map, the kernel-selection predicates
+// and the walking direction of the next tile kernel.
+struct TrainStep {
+    bf_handle h;
+    hipStream_t s;
+    int B, H, W, N, nb, unit;       // nb: block = conv_0 [+ act] , conv_j + BN [+ act] (j >= 1), last one linear, + skip
+                                    // unit: floats from convolution kernel j >= 1 of a block to the next (gamma in between)
+    int64_t npix;
+    double count;
+    TrainLayout L;
+    float* w;                       // workspace
+    float* partial;
+    double* stage1;
+    bool h3t;                       // split-f16 arithmetic (train_arith)
+    bool fwd_block, bwd_block;      // whole blocks in one kernel (train_fwd_h3t.hip / train_bwd_h3t.hip)
+    bool fused_bwd;                 // weight + data gradient of a convolution in one kernel (train_bwd_h3.hip)
+    bool bfold;                     // bwd_block with the BatchNorm-backward finalisation in the next launch's prologue
+    int launch_no;
 
-    const int h3t = h->train_arith == 1;
-    if (N > 0) {
-        if (h3t) {
-            BF_HIP(bf_launch_pack_h3_train(params, h->p_blocks, h->p_block_stride, w + L.wpack, N, nb, unit, s), "pack_h3_train");
-        } else {
-            hipLaunchKernelGGL(pack_all_convs_kernel, dim3(N * 2 * nb), dim3(256), 0, s, params, h->p_blocks, h->p_block_stride,
-                               w + L.wpack, (int64_t)2 * nb * BF_TRAIN_PACK_STRIDE, 1, nb, unit);
-            BF_HIP(hipGetLastError(), "pack_all_convs");
-        }
+    float* ACT(int64_t i) const { return w + L.acts + i * L.act_floats; }
+    // buffer map: A_i = ACT(i) (i = 0..N: block inputs / outputs) ; T(i,j) = input of convolution j >= 1 of block i (the
+    // activated output of convolution j-1) ; C(i,j) = raw output of convolution j >= 1 (in front of its BatchNorm)
+    float* A(int i) const { return ACT(i); }
+    float* T(int i, int j) const { return ACT(N + 1 + (int64_t)i * (nb - 1) + (j - 1)); }
+    float* C(int i, int j) const { return ACT(N + 1 + (int64_t)N * (nb - 1) + (int64_t)i * (nb - 1) + (j - 1)); }
+    // gradient buffers: 0 = dA (the head's output) and two spares; the fused kernels ping-pong between them
+    float* gbuf(int k) const { return ACT(N + 1 + k + 2 * (int64_t)N * (nb - 1)); }
+    // a gradient buffer that is neither g nor dA (the fused backward kernels read their operands with a halo: never in place)
+    float* spare_gbuf(const float* g, const float* dA) const
+    {
+        for (int k = 0; k < 3; ++k)
+            if (gbuf(k) != g && gbuf(k) != dA) return gbuf(k);
+        return nullptr;
     }
+    int64_t conv_off(int j) const { return j == 0 ? (int64_t)0 : 2304 + (int64_t)(j - 1) * unit; }     // inside a block's parameters
+    int64_t bn_idx(int i, int j) const { return (int64_t)i * (nb - 1) + (j - 1); }                       // BatchNorm of convolution j >= 1
+    int bwd_grid() const { return bwd_block ? bf_bwd_block_h3t_grid(B, H, W) : bf_bwd3x3_h3_grid(B, H, W); }
+
     // every tile kernel of the step reads what the one before it wrote: alternate the walking direction (train_zigzag)
-    int launch_no = 0;
-    auto next_reverse = [&]() { return h->train_zigzag ? (launch_no++ & 1) : 0; };
-    auto conv = [&](ConvArgs& ca, int epi) {
+    int next_reverse() { return h->train_zigzag ? (launch_no++ & 1) : 0; }
+    hipError_t conv(ConvArgs& ca, int epi)
+    {
         if (!h3t) return bf_launch_conv3x3_c16(ca, epi, s);
         ca.reverse = next_reverse();
         return bf_launch_conv3x3_h3(ca, epi, s);
-    };
-    auto wgrad = [&](const float* xx, const float* dyy, float* dw) {
+    }
+    hipError_t wgrad(const float* xx, const float* dyy, float* dw) const
+    {
         return h3t ? bf_launch_wgrad3x3_h3(xx, dyy, partial, dw, B, H, W, s) : bf_launch_wgrad3x3_c16(xx, dyy, partial, dw, B, H, W, s);
-    };
-    hipLaunchKernelGGL(premultiply_head_kernel, dim3(1), dim3(64), 0, s, params + h->p_head0, params + h->p_head1, d.head_filters,
-                       d.out_channels, w + L.wh);
-    BF_HIP(hipGetLastError(), "premultiply_head");
+    }
+};
 
-    // ---- forward, training mode (hydra(noisy, training=True), train_loop.py:249-251, 277) ----
+static TrainStep make_train_step(bf_handle h, int B, int H, int W, const TrainLayout& L, void* ws, hipStream_t s)
+{
+    const bf_resnet_desc& d = h->d;
+    TrainStep t;
+    t.h = h; t.s = s; t.B = B; t.H = H; t.W = W; t.N = d.no_layers; t.nb = d.block_convs; t.unit = d.use_bn ? 2320 : 2304;
+    t.npix = (int64_t)B * H * W; t.count = (double)t.npix;
+    t.L = L; t.w = (float*)ws; t.partial = t.w + L.partial;
+    t.stage1 = reinterpret_cast<double*>(t.w + L.stage1);     // (offset is a multiple of 2 floats: 8-byte aligned)
+    t.h3t = h->train_arith == 1;
+    t.launch_no = 0;
+    // whole blocks in one kernel (train_fwd_h3t.hip): [3,3] blocks, BatchNorm on the second convolution, the split-f16 arithmetic,
+    // images up to 256 columns, and a forward of enough rows that its bands (rows + 6 steps each) keep 256 workgroups busy
+    t.fwd_block = t.h3t && h->train_fwd_block && h->train_fused_fwd && t.nb == 2 && d.use_bn && bf_fwd_block_h3t_supports(H, W) &&
+                  (h->train_fwd_block == 2 || (int64_t)B * H >= 4096);
+    // the whole backward of a block in one kernel that RECOMPUTES T_i from A_i (train_bwd_h3t.hip): same kind of block, any width
+    const int64_t bwd_strips = (W + 127) / 128;
+    t.bwd_block = t.h3t && h->train_bwd_block && h->train_fused_bwd && t.nb == 2 && d.use_bn && bf_bwd_block_h3t_supports(H, W) &&
+                  (h->train_bwd_block == 2 || (int64_t)B * H * bwd_strips >= 8192);
+    t.fused_bwd = t.h3t && h->train_fused_bwd;
+    // train_fold_finalize with the block backward kernel: launch i reads the sums launch i + 1 wrote and finalises them in its prologue,
+    // so the sums go to two buffers in turn (both behind the weight-gradient slots inside `partial`)
+    const int64_t bg = t.bwd_grid();
+    t.bfold = t.bwd_block && h->train_fold_finalize != 0 && bg * 2304 + 2 * bg * 32 <= L.partial_floats;
+    return t;
+}
+
+// "fwd: <kernels>; bwd: <kernels>" of bf_get_train_kernels
+static std::string train_kernel_names(const TrainStep& t)
+{
+    const bf_engine& e = *t.h;
+    const char* fwd = t.fwd_block ? "fwd_block_h3t_kernel"
+                      : !t.h3t    ? "conv3x3_c16_kernel"
+                      : e.train_fused_fwd && t.nb >= 2 && e.d.use_bn ? "conv3x3_h3_kernel<.., PRE> + conv3x3_h3_kernel" : "conv3x3_h3_kernel";
+    const char* bwd = t.bwd_block   ? "bwd_block_h3t_kernel"
+                      : t.fused_bwd ? "bwd3x3_h3_kernel<true, 8> + bwd3x3_h3_kernel<false, 36>"
+                      : t.h3t       ? "wgrad3x3_h3_kernel + conv3x3_h3_kernel" : "wgrad3x3_c16_kernel + conv3x3_c16_kernel";
+    return std::string("fwd: ") + fwd + "; bwd: " + bwd;
+}
+
+// ---- forward, training mode (hydra(noisy, training=True), train_loop.py:249-251, 277) ----
+static int train_forward(TrainStep& t, const float* params, float* state, const float* noisy)
+{
+    bf_handle h = t.h;
+    const bf_resnet_desc& d = h->d;
+    const TrainLayout& L = t.L;
+    hipStream_t s = t.s;
+    float* w = t.w;
+    const int B = t.B, H = t.H, W = t.W, N = t.N, nb = t.nb;
     BaseConvArgs ba;
-    ba.in = noisy; ba.out = A(0); ba.w = params + h->p_base;
+    ba.in = noisy; ba.out = t.A(0); ba.w = params + h->p_base;
     ba.B = B; ba.Hs = H; ba.Ws = W; ba.H = H; ba.W = W; ba.cin = d.in_channels; ba.k = d.kernel_size; ba.in_is_u8 = 0;
     ba.act_relu = 0; ba.v_min = d.v_min; ba.v_max = d.v_max; ba.out_split = 0; ba.status = nullptr;
     BF_HIP(bf_launch_base_conv(ba, s), "base_conv");
     const int conv_grid = bf_conv3x3_c16_grid(B, H, W);
     const bool relu = d.activation == BF_ACT_RELU;
     bool pending_affine = false;
-    // whole blocks in one kernel (train_fwd_h3t.hip): [3,3] blocks, BatchNorm on the second convolution, the split-f16 arithmetic,
-    // images up to 256 columns, and a forward of enough rows that its bands (rows + 6 steps each) keep 256 workgroups busy
-    const bool fwd_block = h3t && h->train_fwd_block && h->train_fused_fwd && nb == 2 && d.use_bn && bf_fwd_block_h3t_supports(H, W) &&
-                           (h->train_fwd_block == 2 || (int64_t)B * H >= 4096);
-    // the whole backward of a block in one kernel that RECOMPUTES T_i from A_i (train_bwd_h3t.hip): same kind of block, any width
-    const int64_t bwd_strips = (W + 127) / 128;
-    const bool bwd_block = h3t && h->train_bwd_block && h->train_fused_bwd && nb == 2 && d.use_bn && bf_bwd_block_h3t_supports(H, W) &&
-                           (h->train_bwd_block == 2 || (int64_t)B * H * bwd_strips >= 8192);
-    const bool need_t = !bwd_block;                         // the per-convolution backward kernels read T_i
+    const bool need_t = !t.bwd_block;                       // the per-convolution backward kernels read T_i
     for (int i = 0; i < N; ++i) {
         const float* wp = w + L.wpack + (int64_t)i * 2 * nb * BF_TRAIN_PACK_STRIDE;        // forward packs 0..nb-1, then data-gradient packs
-        if (fwd_block) {
+        if (t.fwd_block) {
             // A_i = A_{i-1} + bn(C_{i-1}) on load ; T_i = act(conv_0 A_i) ; C_i = conv_1 T_i + its batch statistics.
             // train_fold_finalize: the BatchNorm finalisation of block i - 1 runs in THIS launch's prologue (every workgroup sums that
             // block's partials itself; two partial buffers in turn), so a forward is one launch per block instead of two
             const int fgrid = bf_fwd_block_h3t_grid(B, H, W);
             const int64_t pp = ((int64_t)fgrid * 32 + 63) / 64 * 64;
             const bool fold = h->train_fold_finalize != 0;
-            float* part_i = fold ? partial + (i & 1) * pp : partial;
+            float* part_i = fold ? t.partial + (i & 1) * pp : t.partial;
             FwdBlockH3Args fa;
             memset(&fa, 0, sizeof(fa));
-            fa.B = B; fa.H = H; fa.W = W; fa.reverse = next_reverse(); fa.act_relu = relu;
-            fa.x = A(i);
+            fa.B = B; fa.H = H; fa.W = W; fa.reverse = t.next_reverse(); fa.act_relu = relu;
+            fa.x = t.A(i);
             if (pending_affine) {
-                fa.x = A(i - 1); fa.pre_c = C(i - 1, 1); fa.a_out = A(i);
-                fa.pre_scale = w + L.bn_scale + bn_idx(i - 1, 1) * 32; fa.pre_shift = fa.pre_scale + 16;
+                fa.x = t.A(i - 1); fa.pre_c = t.C(i - 1, 1); fa.a_out = t.A(i);
+                fa.pre_scale = w + L.bn_scale + t.bn_idx(i - 1, 1) * 32; fa.pre_shift = fa.pre_scale + 16;
                 if (fold) {
-                    fa.fin_partial = partial + ((i - 1) & 1) * pp; fa.fin_nblk = fgrid; fa.fin_count = count;
-                    fa.fin_gamma = params + h->p_blocks + (i - 1) * h->p_block_stride + conv_off(1) + 2304;
-                    fa.fin_mm = state + bn_idx(i - 1, 1) * 32; fa.fin_mv = fa.fin_mm + 16;
+                    fa.fin_partial = t.partial + ((i - 1) & 1) * pp; fa.fin_nblk = fgrid; fa.fin_count = t.count;
+                    fa.fin_gamma = params + h->p_blocks + (i - 1) * h->p_block_stride + t.conv_off(1) + 2304;
+                    fa.fin_mm = state + t.bn_idx(i - 1, 1) * 32; fa.fin_mv = fa.fin_mm + 16;
                     fa.fin_eps = d.bn_eps; fa.fin_momentum = d.bn_momentum;
-                    fa.fin_scale = w + L.bn_scale + bn_idx(i - 1, 1) * 32; fa.fin_meaninv = w + L.bn_meaninv + bn_idx(i - 1, 1) * 32;
+                    fa.fin_scale = w + L.bn_scale + t.bn_idx(i - 1, 1) * 32; fa.fin_meaninv = w + L.bn_meaninv + t.bn_idx(i - 1, 1) * 32;
                 }
                 pending_affine = false;
             }
-            fa.t_out = need_t ? T(i, 1) : nullptr; fa.c_out = C(i, 1);
+            fa.t_out = need_t ? t.T(i, 1) : nullptr; fa.c_out = t.C(i, 1);
             fa.wpack0 = wp; fa.wpack1 = wp + BF_TRAIN_PACK_STRIDE; fa.stats = part_i;
             BF_HIP(bf_launch_fwd_block_h3t(fa, s), "fwd_block_h3t");
             if (fold && i + 1 < N) {
                 pending_affine = true;                              // block i + 1 finalises this BatchNorm itself
                 continue;
             }
-            float* scale = w + L.bn_scale + bn_idx(i, 1) * 32;
-            BF_HIP(bf_launch_bn_finalize(part_i, fgrid, count, params + h->p_blocks + i * h->p_block_stride + conv_off(1) + 2304,
-                                         state + bn_idx(i, 1) * 32, state + bn_idx(i, 1) * 32 + 16, d.bn_eps, d.bn_momentum, scale,
-                                         scale + 16, w + L.bn_meaninv + bn_idx(i, 1) * 32, stage1, s), "bn_finalize");
+            float* scale = w + L.bn_scale + t.bn_idx(i, 1) * 32;
+            BF_HIP(bf_launch_bn_finalize(part_i, fgrid, t.count, params + h->p_blocks + i * h->p_block_stride + t.conv_off(1) + 2304,
+                                         state + t.bn_idx(i, 1) * 32, state + t.bn_idx(i, 1) * 32 + 16, d.bn_eps, d.bn_momentum, scale,
+                                         scale + 16, w + L.bn_meaninv + t.bn_idx(i, 1) * 32, t.stage1, s), "bn_finalize");
             if (i + 1 < N) pending_affine = true;
-            else BF_HIP(bf_launch_affine_add(A(i), C(i, 1), scale, scale + 16, A(i + 1), npix, s), "affine_add");
+            else BF_HIP(bf_launch_affine_add(t.A(i), t.C(i, 1), scale, scale + 16, t.A(i + 1), t.npix, s), "affine_add");
             continue;
         }
         for (int j = 0; j < nb; ++j) {
@@ -954,42 +977,52 @@ extern "C" int bf_train_step(bf_handle h, const float* params, float* state, con
             ConvArgs ca;
             memset(&ca, 0, sizeof(ca));
             ca.B = B; ca.H = H; ca.W = W;
-            ca.in = j == 0 ? A(i) : T(i, j); ca.wpack = wp + (int64_t)j * BF_TRAIN_PACK_STRIDE;
+            ca.in = j == 0 ? t.A(i) : t.T(i, j); ca.wpack = wp + (int64_t)j * BF_TRAIN_PACK_STRIDE;
             if (j == 0 && pending_affine) {
                 // A(i) = A(i-1) + scale * C(i-1, last) + shift has not been formed yet: this convolution does it on load
-                ca.in = A(i - 1); ca.pre_c = C(i - 1, nb - 1); ca.pre_out = A(i);
-                ca.pre_scale = w + L.bn_scale + bn_idx(i - 1, nb - 1) * 32; ca.pre_shift = ca.pre_scale + 16;
+                ca.in = t.A(i - 1); ca.pre_c = t.C(i - 1, nb - 1); ca.pre_out = t.A(i);
+                ca.pre_scale = w + L.bn_scale + t.bn_idx(i - 1, nb - 1) * 32; ca.pre_shift = ca.pre_scale + 16;
                 pending_affine = false;
             }
             if (bn) {
                 // conv -> BatchNorm (batch statistics ride in the convolution's epilogue) -> [activation | + skip]
-                float* scale = w + L.bn_scale + bn_idx(i, j) * 32;
-                ca.out = C(i, j); ca.stats = partial;
-                BF_HIP(conv(ca, EPI_STATS), "conv + statistics");
-                BF_HIP(bf_launch_bn_finalize(partial, conv_grid, count, params + h->p_blocks + i * h->p_block_stride + conv_off(j) + 2304,
-                                             state + bn_idx(i, j) * 32, state + bn_idx(i, j) * 32 + 16, d.bn_eps, d.bn_momentum, scale,
-                                             scale + 16, w + L.bn_meaninv + bn_idx(i, j) * 32, stage1, s), "bn_finalize");
+                float* scale = w + L.bn_scale + t.bn_idx(i, j) * 32;
+                ca.out = t.C(i, j); ca.stats = t.partial;
+                BF_HIP(t.conv(ca, EPI_STATS), "conv + statistics");
+                BF_HIP(bf_launch_bn_finalize(t.partial, conv_grid, t.count, params + h->p_blocks + i * h->p_block_stride + t.conv_off(j) + 2304,
+                                             state + t.bn_idx(i, j) * 32, state + t.bn_idx(i, j) * 32 + 16, d.bn_eps, d.bn_momentum, scale,
+                                             scale + 16, w + L.bn_meaninv + t.bn_idx(i, j) * 32, t.stage1, s), "bn_finalize");
                 // block i+1's conv_0 forms A(i+1) on load.  (The head kernel doing the same for the last block was tried: its register
                 // count went past 256, one wave per SIMD, +105 us in the head for the 79 us of affine_add.)
-                if (last && h3t && h->train_fused_fwd && i + 1 < N && nb >= 2) pending_affine = true;
-                else if (last) BF_HIP(bf_launch_affine_add(A(i), C(i, j), scale, scale + 16, A(i + 1), npix, s), "affine_add");
-                else BF_HIP(bf_launch_affine_act(C(i, j), scale, scale + 16, T(i, j + 1), relu, npix, s), "affine_act");
+                if (last && t.h3t && h->train_fused_fwd && i + 1 < N && nb >= 2) pending_affine = true;
+                else if (last) BF_HIP(bf_launch_affine_add(t.A(i), t.C(i, j), scale, scale + 16, t.A(i + 1), t.npix, s), "affine_add");
+                else BF_HIP(bf_launch_affine_act(t.C(i, j), scale, scale + 16, t.T(i, j + 1), relu, t.npix, s), "affine_act");
             } else if (last) {
                 // no BatchNorm on the block's last convolution (one-convolution block, or use_bn off): linear, + skip
-                ca.out = A(i + 1); ca.res = A(i);
-                BF_HIP(conv(ca, EPI_RES), "conv + skip");
+                ca.out = t.A(i + 1); ca.res = t.A(i);
+                BF_HIP(t.conv(ca, EPI_RES), "conv + skip");
             } else {
-                ca.out = T(i, j + 1);
-                BF_HIP(conv(ca, relu ? EPI_RELU : 0), "conv + activation");
+                ca.out = t.T(i, j + 1);
+                BF_HIP(t.conv(ca, relu ? EPI_RELU : 0), "conv + activation");
             }
         }
     }
+    return BF_OK;
+}
 
-    // ---- head forward + loss + head backward ---------------------------------------------------
-    const double numel = (double)npix * d.out_channels;
+// ---- head forward + loss + head backward: dL/dA_N * S to gbuf(0), the head's gradients and the data-term losses; *grad_unscale = 1 / S ----
+static int train_head_and_loss(TrainStep& t, const float* params, const float* gt, const bf_loss_desc* loss, float* predictions,
+                               float* grads, float* losses, float* grad_unscale)
+{
+    bf_handle h = t.h;
+    const bf_resnet_desc& d = h->d;
+    hipStream_t s = t.s;
+    const int B = t.B, H = t.H, W = t.W;
+    const bool extra_terms = loss->ssim_multiplier > 0.f || loss->mse_multiplier > 0.f;     // use_ssim / use_mse (loss.py:174-179)
+    const double numel = (double)t.npix * d.out_channels;
     HeadTrainArgs ta;
-    ta.feat = A(N); ta.wh = w + L.wh;
-    ta.gt = gt; ta.pred = predictions; ta.dfeat = dA; ta.partial = partial; ta.dextra = nullptr;
+    ta.feat = t.A(t.N); ta.wh = t.w + t.L.wh;
+    ta.gt = gt; ta.pred = predictions; ta.dfeat = t.gbuf(0); ta.partial = t.partial; ta.dextra = nullptr;
     ta.B = B; ta.H = H; ta.W = W; ta.cout = d.out_channels; ta.denormalize = d.denormalize;
     ta.v_min = d.v_min; ta.v_max = d.v_max; ta.hinge = loss->hinge; ta.cutoff = loss->cutoff;
     ta.dscale = loss->mae_multiplier > 0.f ? (float)((double)loss->mae_multiplier * loss->depth_weight / numel) : 0.f;
@@ -1000,29 +1033,29 @@ extern "C" int bf_train_step(bf_handle h, const float* params, float* state, con
     // tools/exp/train_batch_rep.py).  The head hands the blocks dfeat * S, S the power of two next to numel / (multiplier *
     // depth_weight); every backward operator is linear in dy, and the block / base gradients are multiplied by 1 / S (exact)
     // before the regularisers are added.  The exact-fp32 arithmetic runs with S = 1 as before.
-    float grad_unscale = 1.0f;
+    *grad_unscale = 1.0f;
     ta.dfeat_scale = 1.0f;
-    if (h3t) {
+    if (t.h3t) {
         const double per = (loss->mae_multiplier > 0.f ? (double)loss->mae_multiplier : 1.0) * (loss->depth_weight > 0.f ? loss->depth_weight : 1.0) / numel;
         int ex = 0;
         (void)frexp(1.0 / per, &ex);
         ex = ex - 1 < 0 ? 0 : (ex - 1 > 40 ? 40 : ex - 1);
         ta.dfeat_scale = ldexpf(1.0f, ex);
-        grad_unscale = ldexpf(1.0f, -ex);
+        *grad_unscale = ldexpf(1.0f, -ex);
     }
     const int hgrid = bf_head_train_grid(B, H, W);
     float* scal = nullptr;
     if (extra_terms) {
         // pass A: prediction + per-image sums; then the additive gradient of the RMSE / SSIM terms; pass B below adds it
-        const int64_t pe = npix * d.out_channels;
-        float* ex = w + L.extra;
+        const int64_t pe = t.npix * d.out_channels;
+        float* ex = t.w + t.L.extra;
         float* predbuf = predictions ? predictions : ex;
-        float *dextra = ex + pe, *maps = ex + 2 * pe, *ssim_partial = ex + 5 * (int64_t)npix * 4;
+        float *dextra = ex + pe, *maps = ex + 2 * pe, *ssim_partial = ex + 5 * (int64_t)t.npix * 4;
         float* coef = ssim_partial + 4096;
         scal = coef + align_up(B, 64);
         ta.pred = predbuf;
         BF_HIP(bf_launch_head_train(ta, hgrid, s), "head_train (prediction pass)");
-        BF_HIP(bf_launch_loss_extra(predbuf, gt, B, H, W, d.out_channels, partial, hgrid / B, loss->hinge, loss->cutoff,
+        BF_HIP(bf_launch_loss_extra(predbuf, gt, B, H, W, d.out_channels, t.partial, hgrid / B, loss->hinge, loss->cutoff,
                                     loss->mse_multiplier > 0.f ? loss->mse_multiplier : 0.f,
                                     loss->ssim_multiplier > 0.f ? loss->ssim_multiplier : 0.f, loss->depth_weight, 255.0f, maps,
                                     ssim_partial, coef, scal, dextra, s), "loss_extra");
@@ -1030,7 +1063,7 @@ extern "C" int bf_train_step(bf_handle h, const float* params, float* state, con
         ta.dextra = dextra;
     }
     BF_HIP(bf_launch_head_train(ta, hgrid, s), "head_train");
-    hipLaunchKernelGGL(head_finalize_kernel, dim3(1), dim3(1024), 0, s, partial, hgrid, hgrid / B, B, numel,
+    hipLaunchKernelGGL(head_finalize_kernel, dim3(1), dim3(1024), 0, s, t.partial, hgrid, hgrid / B, B, numel,
                        (double)H * W * d.out_channels, params + h->p_head0, params + h->p_head1, d.head_filters, d.out_channels,
                        grads + h->p_head0, grads + h->p_head1, losses, loss->mae_multiplier, loss->depth_weight);
     BF_HIP(hipGetLastError(), "head_finalize");
@@ -1038,28 +1071,31 @@ extern "C" int bf_train_step(bf_handle h, const float* params, float* state, con
         BF_HIP(bf_launch_loss_extra_finalize(scal, B, H, W, d.out_channels, loss->mse_multiplier > 0.f ? loss->mse_multiplier : 0.f,
                                              loss->ssim_multiplier > 0.f ? loss->ssim_multiplier : 0.f, loss->depth_weight, losses, s),
                "loss_extra_finalize");
+    return BF_OK;
+}
 
-    // ---- backward through the blocks -----------------------------------------------------------
-    // g = dL/d(block output) arrives in dA.  Per convolution j = nb-1 .. 0: [BatchNorm backward: g -> dc, dgamma] ; weight
-    // gradient from (input of conv j, dc) ; data gradient through conv j -- for j >= 1 written over T(i,j) with the ReLU mask
-    // of the activation that produced T(i,j), for j = 0 added to dA (the skip).
-    int64_t n4 = npix * 4;
-    int bgrid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    const bool fused_bwd = h3t && h->train_fused_bwd;
-    // gradient buffers: dA (the head's output) and two spares; the fused kernel ping-pongs between them
-    float* const gbuf[3] = {dA, ACT(N + 2 + 2 * (int64_t)N * (nb - 1)), ACT(N + 3 + 2 * (int64_t)N * (nb - 1))};
-    // both convolutions of a block in one launch: [3,3] blocks, BatchNorm on the second convolution, ReLU between them
-    const bool fused_bwd2 = fused_bwd && h->train_fused_bwd2 && nb == 2 && d.use_bn && relu;
-    h->train_kernels = std::string("fwd: ") + (fwd_block ? "fwd_block_h3t_kernel" : h3t ? (h->train_fused_fwd && nb >= 2 && d.use_bn ? "conv3x3_h3_kernel<.., PRE> + conv3x3_h3_kernel" : "conv3x3_h3_kernel")
-                                                   : "conv3x3_c16_kernel")
-                       + "; bwd: " + (bwd_block ? "bwd_block_h3t_kernel" : fused_bwd2 ? "bwd2_h3_kernel" : fused_bwd ? "bwd3x3_h3_kernel<true, 8> + bwd3x3_h3_kernel<false, 36>"
-                                                 : h3t ? "wgrad3x3_h3_kernel + conv3x3_h3_kernel" : "wgrad3x3_c16_kernel + conv3x3_c16_kernel");
-    const int bwd_grid = bwd_block ? bf_bwd_block_h3t_grid(B, H, W) : fused_bwd2 ? bf_bwd2_h3_grid(B, H, W) : bf_bwd3x3_h3_grid_ex(B, H, W, h->train_bwd_dbuf);
+// ---- backward through the blocks: block weight / gamma gradients to grads, *dA_out = the buffer that holds dL/dA_0 -------------
+// g = dL/d(block output) arrives in dA = gbuf(0).  Per convolution j = nb-1 .. 0: [BatchNorm backward: g -> dc, dgamma] ; weight
+// gradient from (input of conv j, dc) ; data gradient through conv j -- for j >= 1 written over T(i,j) with the ReLU mask
+// of the activation that produced T(i,j), for j = 0 added to dA (the skip).
+static int train_backward(TrainStep& t, const float* params, float* grads, float** dA_out)
+{
+    bf_handle h = t.h;
+    const bf_resnet_desc& d = h->d;
+    const TrainLayout& L = t.L;
+    hipStream_t s = t.s;
+    float* w = t.w;
+    float* partial = t.partial;
+    const int B = t.B, H = t.H, W = t.W, N = t.N, nb = t.nb;
+    const bool h3t = t.h3t, fused_bwd = t.fused_bwd, bfold = t.bfold;
+    const bool relu = d.activation == BF_ACT_RELU;
+    const int conv_grid = bf_conv3x3_c16_grid(B, H, W);
+    const int64_t n4 = t.npix * 4;
+    const int bgrid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+    const int bwd_grid = t.bwd_grid();
     float* bwd_stats = partial + (int64_t)bwd_grid * 2304;
-    // train_fold_finalize with the block backward kernel: launch i reads the sums launch i + 1 wrote and finalises them in its prologue,
-    // so the sums go to two buffers in turn (both behind the weight-gradient slots inside `partial`)
-    const bool bfold = bwd_block && h->train_fold_finalize != 0 && (int64_t)bwd_grid * 2304 + 2 * (int64_t)bwd_grid * 32 <= L.partial_floats;
     auto bstats = [&](int i) { return bfold ? bwd_stats + (int64_t)(i & 1) * bwd_grid * 32 : bwd_stats; };
+    float* dA = t.gbuf(0);
     for (int i = N - 1; i >= 0; --i) {
         const float* wp = w + L.wpack + (int64_t)i * 2 * nb * BF_TRAIN_PACK_STRIDE;
         float* gblk = grads + h->p_blocks + i * h->p_block_stride;
@@ -1071,39 +1107,37 @@ extern "C" int bf_train_step(bf_handle h, const float* params, float* state, con
                 // sum dy, sum dy*c: for the block's last BatchNorm they come from the data-gradient kernel of the block above
                 // when it produced dA (split-f16 path: its epilogue accumulates them), else from the reduction kernel
                 const bool fused_sums = h3t && last && i < N - 1;
-                if (!fused_sums) BF_HIP(bf_launch_bn_bwd_reduce(g, C(i, j), partial, npix, bgrid, s), "bn_bwd_reduce");
+                if (!fused_sums) BF_HIP(bf_launch_bn_bwd_reduce(g, t.C(i, j), partial, t.npix, bgrid, s), "bn_bwd_reduce");
                 if (!(bfold && fused_sums))
                 BF_HIP(bf_launch_bn_bwd_finalize(fused_sums && fused_bwd ? bstats(i + 1) : partial,
-                                                 fused_sums ? (fused_bwd ? bwd_grid : conv_grid) : bgrid, count,
-                                                 params + h->p_blocks + i * h->p_block_stride + conv_off(j) + 2304,
-                                                 w + L.bn_meaninv + bn_idx(i, j) * 32, w + L.coef, gblk + conv_off(j) + 2304, stage1, s),
+                                                 fused_sums ? (fused_bwd ? bwd_grid : conv_grid) : bgrid, t.count,
+                                                 params + h->p_blocks + i * h->p_block_stride + t.conv_off(j) + 2304,
+                                                 w + L.bn_meaninv + t.bn_idx(i, j) * 32, w + L.coef, gblk + t.conv_off(j) + 2304, t.stage1, s),
                        "bn_bwd_finalize");
                 if (!fused_bwd) {
-                    BF_HIP(bf_launch_bn_bwd_apply(g, C(i, j), w + L.coef, C(i, j), npix, s), "bn_bwd_apply");
-                    dy = C(i, j);
+                    BF_HIP(bf_launch_bn_bwd_apply(g, t.C(i, j), w + L.coef, t.C(i, j), t.npix, s), "bn_bwd_apply");
+                    dy = t.C(i, j);
                 }
             }
-            if (bwd_block) {
+            if (t.bwd_block) {
                 // one row-streaming kernel for the whole block, T recomputed from A(i): dc = k1 g + k2 c + k3 ; T = act(conv_0 A) ;
                 // dw1 = T^T dc ; dT = dgrad_1(dc) * (T > 0) ; dw0 = A^T dT ; dA' = dgrad_0(dT) + g [+ the sums of the BatchNorm in front]
                 BwdBlockH3Args fa;
                 memset(&fa, 0, sizeof(fa));
-                fa.B = B; fa.H = H; fa.W = W; fa.act_relu = relu; fa.reverse = next_reverse();
-                fa.a = A(i); fa.g = g; fa.c = C(i, 1); fa.coef = w + L.coef;
+                fa.B = B; fa.H = H; fa.W = W; fa.act_relu = relu; fa.reverse = t.next_reverse();
+                fa.a = t.A(i); fa.g = g; fa.c = t.C(i, 1); fa.coef = w + L.coef;
                 if (bfold && i < N - 1) {                           // the sums came from launch i + 1: finalised in this launch's prologue
-                    fa.fin_partial = bstats(i + 1); fa.fin_nblk = bwd_grid; fa.fin_count = count;
-                    fa.fin_gamma = params + h->p_blocks + i * h->p_block_stride + conv_off(1) + 2304;
-                    fa.fin_meaninv = w + L.bn_meaninv + bn_idx(i, 1) * 32;
-                    fa.fin_dgamma = gblk + conv_off(1) + 2304;
+                    fa.fin_partial = bstats(i + 1); fa.fin_nblk = bwd_grid; fa.fin_count = t.count;
+                    fa.fin_gamma = params + h->p_blocks + i * h->p_block_stride + t.conv_off(1) + 2304;
+                    fa.fin_meaninv = w + L.bn_meaninv + t.bn_idx(i, 1) * 32;
+                    fa.fin_dgamma = gblk + t.conv_off(1) + 2304;
                 }
                 fa.wfwd0 = wp; fa.wdg0 = wp + (int64_t)nb * BF_TRAIN_PACK_STRIDE; fa.wdg1 = wp + (int64_t)(nb + 1) * BF_TRAIN_PACK_STRIDE;
                 fa.wpartial1 = w + L.wslots + ((int64_t)i * nb + 1) * L.wslot_floats;
                 fa.wpartial0 = w + L.wslots + ((int64_t)i * nb + 0) * L.wslot_floats;
                 fa.stats = bstats(i);
-                if (i > 0) fa.bnc = C(i - 1, nb - 1);
-                float* out = nullptr;
-                for (int k = 0; k < 3 && !out; ++k)
-                    if (gbuf[k] != g) out = gbuf[k];
+                if (i > 0) fa.bnc = t.C(i - 1, nb - 1);
+                float* out = t.spare_gbuf(g, dA);                   // (g == dA here)
                 fa.out = out;
                 // option "timing": one HIP-event pair around EVERY launch of this kernel (ring of BF_TIMING_RING pairs; bf_get_timing
                 // returns their sum and count: bench.py's live roofline of the training step, measured inside real steps)
@@ -1119,40 +1153,17 @@ extern "C" int bf_train_step(bf_handle h, const float* params, float* state, con
                 dA = out;
                 break;                                              // both convolutions done
             }
-            if (fused_bwd2) {
-                // one kernel for the whole block: dc = k1 g + k2 c + k3 ; dw2 = T^T dc ; dT = dgrad2(dc) * (T > 0) (LDS only) ;
-                // dw1 = A^T dT ; dA' = dgrad1(dT) + g [+ the sums of the BatchNorm in front]
-                Bwd2H3Args fa;
-                memset(&fa, 0, sizeof(fa));
-                fa.B = B; fa.H = H; fa.W = W;
-                fa.t = T(i, 1); fa.a = A(i); fa.dy = g; fa.c = C(i, 1); fa.coef = w + L.coef;
-                fa.wpack2 = wp + (int64_t)(nb + 1) * BF_TRAIN_PACK_STRIDE; fa.wpack1 = wp + (int64_t)nb * BF_TRAIN_PACK_STRIDE;
-                fa.wpartial2 = w + L.wslots + ((int64_t)i * nb + 1) * L.wslot_floats;
-                fa.wpartial1 = w + L.wslots + ((int64_t)i * nb + 0) * L.wslot_floats;
-                fa.stats = bwd_stats; fa.reverse = next_reverse();
-                if (i > 0) fa.bnc = C(i - 1, nb - 1);
-                float* out = nullptr;
-                for (int k = 0; k < 3 && !out; ++k)
-                    if (gbuf[k] != g) out = gbuf[k];
-                fa.out = out;
-                BF_HIP(bf_launch_bwd2_h3(fa, s), "bwd2_h3");
-                g = out;
-                dA = out;
-                break;                                              // both convolutions done
-            }
             if (fused_bwd) {
                 // one kernel: [dc = k1 g + k2 c + k3] ; dw = x^T dc ; dx = dgrad(dc) [* mask | + skip]
                 BwdH3Args fa;
                 memset(&fa, 0, sizeof(fa));
                 fa.B = B; fa.H = H; fa.W = W;
-                fa.x = j == 0 ? A(i) : T(i, j);
+                fa.x = j == 0 ? t.A(i) : t.T(i, j);
                 fa.g = g;
-                if (bn) { fa.c = C(i, j); fa.coef = w + L.coef; }
+                if (bn) { fa.c = t.C(i, j); fa.coef = w + L.coef; }
                 fa.wpack = wp + (int64_t)(nb + j) * BF_TRAIN_PACK_STRIDE;
-                fa.wpartial = w + L.wslots + ((int64_t)i * nb + j) * L.wslot_floats; fa.stats = bwd_stats; fa.reverse = next_reverse(); fa.dbuf = h->train_bwd_dbuf;
-                float* out = nullptr;
-                for (int k = 0; k < 3 && !out; ++k)
-                    if (gbuf[k] != g && gbuf[k] != dA) out = gbuf[k];
+                fa.wpartial = w + L.wslots + ((int64_t)i * nb + j) * L.wslot_floats; fa.stats = bwd_stats; fa.reverse = t.next_reverse();
+                float* out = t.spare_gbuf(g, dA);
                 int epi;
                 if (j > 0) {
                     epi = relu ? EPI_MASK : 0;
@@ -1160,7 +1171,7 @@ extern "C" int bf_train_step(bf_handle h, const float* params, float* state, con
                     fa.res = dA;
                     if (g != dA) out = dA;                          // in place over the skip gradient (read at the same element only)
                     epi = EPI_RES;
-                    if (d.use_bn && nb >= 2 && i > 0) { fa.bnc = C(i - 1, nb - 1); epi |= EPI_BNBWD; }
+                    if (d.use_bn && nb >= 2 && i > 0) { fa.bnc = t.C(i - 1, nb - 1); epi |= EPI_BNBWD; }
                 }
                 fa.out = out;
                 BF_HIP(bf_launch_bwd3x3_h3(fa, epi, nullptr, s), "bwd3x3_h3");
@@ -1168,30 +1179,79 @@ extern "C" int bf_train_step(bf_handle h, const float* params, float* state, con
                 if (j == 0) dA = out;                               // (one-convolution block: another buffer than before)
                 continue;
             }
-            BF_HIP(wgrad(j == 0 ? A(i) : T(i, j), dy, gblk + conv_off(j)), "wgrad");
+            BF_HIP(t.wgrad(j == 0 ? t.A(i) : t.T(i, j), dy, gblk + t.conv_off(j)), "wgrad");
             ConvArgs ca;
             memset(&ca, 0, sizeof(ca));
             ca.B = B; ca.H = H; ca.W = W;
             ca.in = dy; ca.wpack = wp + (int64_t)(nb + j) * BF_TRAIN_PACK_STRIDE;
             if (j > 0) {
-                ca.out = T(i, j); ca.mask = T(i, j);
-                BF_HIP(conv(ca, relu ? EPI_MASK : 0), "dgrad");
-                g = T(i, j);
+                ca.out = t.T(i, j); ca.mask = t.T(i, j);
+                BF_HIP(t.conv(ca, relu ? EPI_MASK : 0), "dgrad");
+                g = t.T(i, j);
             } else {
                 ca.out = dA; ca.res = dA;
                 if (h3t && d.use_bn && nb >= 2 && i > 0) {       // dA becomes dy of block i-1's last BatchNorm: its sums ride along
-                    ca.bnc = C(i - 1, nb - 1); ca.stats = partial;
-                    BF_HIP(conv(ca, EPI_RES | EPI_BNBWD), "dgrad + skip");
+                    ca.bnc = t.C(i - 1, nb - 1); ca.stats = partial;
+                    BF_HIP(t.conv(ca, EPI_RES | EPI_BNBWD), "dgrad + skip");
                 } else {
-                    BF_HIP(conv(ca, EPI_RES), "dgrad + skip");
+                    BF_HIP(t.conv(ca, EPI_RES), "dgrad + skip");
                 }
             }
         }
     }
     if (fused_bwd && N > 0)
-        BF_HIP(bf_launch_reduce_wgrad_slots(w + L.wslots, L.wslot_floats, bwd_grid, grads + h->p_blocks, h->p_block_stride, N, nb, unit, s),
+        BF_HIP(bf_launch_reduce_wgrad_slots(w + L.wslots, L.wslot_floats, bwd_grid, grads + h->p_blocks, h->p_block_stride, N, nb, t.unit, s),
                "reduce_wgrad_slots");
-    BF_HIP(bf_launch_base_wgrad(noisy, dA, partial, grads + h->p_base, B, H, W, d.in_channels, d.kernel_size, d.v_min, d.v_max, s),
+    *dA_out = dA;
+    return BF_OK;
+}
+
+extern "C" int bf_train_step(bf_handle h, const float* params, float* state, const float* gt, const float* noisy, int B, int H,
+                             int W, const bf_loss_desc* loss, float* predictions, float* grads, float* losses, void* ws,
+                             int64_t ws_bytes, void* stream)
+{
+    if (!h) return BF_EINVAL;
+    const bf_resnet_desc& d = h->d;
+    if (!params || !gt || !noisy || !loss || !grads || !losses || (h->n_state > 0 && !state))
+        return fail(h, BF_EINVAL, "bf_train_step: NULL argument");
+    if (loss->struct_size != (int32_t)sizeof(bf_loss_desc)) return fail(h, BF_EINVAL, "bf_loss_desc struct_size mismatch");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(h, BF_EINVAL, "batch/height/width must be positive");
+    if (loss->ssim_multiplier > 0.f && (H < 7 || W < 7)) return fail(h, BF_EINVAL, "SSIM needs images of at least 7x7");
+    if (loss->ssim_multiplier > 0.f && !d.denormalize)
+        return fail(h, BF_EUNSUPPORTED, "SSIM term (max_val 255) is built for the denormalised hydra output");
+    if (d.head_activation != BF_ACT_LINEAR) return fail(h, BF_EUNSUPPORTED, "training is built for the linear denoiser head");
+    if (d.block_convs < 1 || d.block_convs > 3) return fail(h, BF_EUNSUPPORTED, "training is built for blocks of 1 to 3 convolutions (got %d)", d.block_convs);
+    if (d.out_channels != d.in_channels) return fail(h, BF_EINVAL, "gt/prediction channel mismatch");
+    const TrainLayout L = train_layout(h, B, H, W);
+    if (!ws || (uintptr_t)ws % 16) return fail(h, BF_EWORKSPACE, "workspace must be a 16-byte aligned device buffer");
+    if (ws_bytes < L.total * 4) return fail(h, BF_EWORKSPACE, "workspace too small: %lld < %lld bytes", (long long)ws_bytes,
+                                            (long long)(L.total * 4));
+    hipStream_t s = (hipStream_t)stream;
+    TrainStep t = make_train_step(h, B, H, W, L, ws, s);
+    if (t.N > 0) {
+        if (t.h3t) {
+            BF_HIP(bf_launch_pack_h3_train(params, h->p_blocks, h->p_block_stride, t.w + L.wpack, t.N, t.nb, t.unit, s), "pack_h3_train");
+        } else {
+            hipLaunchKernelGGL(pack_all_convs_kernel, dim3(t.N * 2 * t.nb), dim3(256), 0, s, params, h->p_blocks, h->p_block_stride,
+                               t.w + L.wpack, (int64_t)2 * t.nb * BF_TRAIN_PACK_STRIDE, 1, t.nb, t.unit);
+            BF_HIP(hipGetLastError(), "pack_all_convs");
+        }
+    }
+    hipLaunchKernelGGL(premultiply_head_kernel, dim3(1), dim3(64), 0, s, params + h->p_head0, params + h->p_head1, d.head_filters,
+                       d.out_channels, t.w + L.wh);
+    BF_HIP(hipGetLastError(), "premultiply_head");
+
+    int rc = train_forward(t, params, state, noisy);
+    if (rc != BF_OK) return rc;
+    float grad_unscale = 1.0f;
+    rc = train_head_and_loss(t, params, gt, loss, predictions, grads, losses, &grad_unscale);
+    if (rc != BF_OK) return rc;
+    h->train_kernels = train_kernel_names(t);
+    float* dA = nullptr;                            // dL/dA_0 after the backward pass
+    rc = train_backward(t, params, grads, &dA);
+    if (rc != BF_OK) return rc;
+
+    BF_HIP(bf_launch_base_wgrad(noisy, dA, t.partial, grads + h->p_base, B, H, W, d.in_channels, d.kernel_size, d.v_min, d.v_max, s),
            "base_wgrad");
     if (grad_unscale != 1.0f) {
         // base + block gradients (everything in front of the head's tensors) back to the loss's own scale
@@ -1199,9 +1259,9 @@ extern "C" int bf_train_step(bf_handle h, const float* params, float* state, con
         BF_HIP(hipGetLastError(), "grad_unscale");
     }
     hipLaunchKernelGGL(regularizer_kernel, dim3(REG_GRID), dim3(1024), 0, s, params, grads, h->n_params, h->n_base, h->p_blocks,
-                       h->p_block_stride, h->p_head0, d.reg_base, d.reg_block, d.reg_head, loss->regularization, stage1,
-                       d.use_bn ? 2320 : 2304);
-    hipLaunchKernelGGL(regularizer_finalize_kernel, dim3(1), dim3(64), 0, s, stage1, loss->regularization, losses);
+                       h->p_block_stride, h->p_head0, d.reg_base, d.reg_block, d.reg_head, loss->regularization, t.stage1,
+                       t.unit);
+    hipLaunchKernelGGL(regularizer_finalize_kernel, dim3(1), dim3(64), 0, s, t.stage1, loss->regularization, losses);
     BF_HIP(hipGetLastError(), "regularizer");
     return BF_OK;
 }
@@ -1370,289 +1430,4 @@ extern "C" int bf_op_adam_step(float* params, const float* grads, float* m, floa
 {
     return adam_ex_core(nullptr, n, params, grads, m, v, iterations, lr, beta_1, beta_2, epsilon, global_clipnorm, clipnorm, clipvalue,
                         tensor_offsets, n_tensors, tensor_scratch, grad_scale, losses, scratch, stream);
-}
-
-// ------------------------------------------------------------------------------------------
-// diagnostics used by tests/ (single-kernel entry points; not part of the drop-in surface)
-// ------------------------------------------------------------------------------------------
-extern "C" int bf_debug_conv3x3(const float* in, const float* w_hwio, float* out, const float* scale, const float* shift,
-                                const float* res, const float* mask, float* stats, float* wpack_scratch, int B, int H, int W,
-                                int epi, int transpose_flip, void* stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    if (bf_launch_pack_conv(w_hwio, wpack_scratch, transpose_flip, s) != hipSuccess) return BF_EHIP;
-    ConvArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.in = in; ca.out = out; ca.wpack = wpack_scratch; ca.scale = scale; ca.shift = shift; ca.res = res; ca.mask = mask;
-    ca.stats = stats; ca.B = B; ca.H = H; ca.W = W;
-    return bf_launch_conv3x3_c16(ca, epi, s) == hipSuccess ? BF_OK : BF_EHIP;
-}
-
-static unsigned long long* g_fused_dbg = nullptr;
-// diagnostic builds (H3_ABLATE=32, tools/stamp_h3.py and its siblings): device buffer of 512*8*8 u64 that receives per-wave phase cycle sums
-extern "C" int bf_debug_set_fused_dbg(void* buf) { g_fused_dbg = (unsigned long long*)buf; return BF_OK; }
-
-extern "C" int bf_debug_conv3x3_grid(int B, int H, int W) { return bf_conv3x3_c16_grid(B, H, W); }
-
-extern "C" int bf_debug_fused_block(const float* in, const float* w1_hwio, const float* w2_hwio, const float* scale,
-                                    const float* shift, float* out, float* wpack_scratch, int B, int H, int W, int act1_relu,
-                                    void* stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    if (bf_launch_pack_conv(w1_hwio, wpack_scratch, 0, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_pack_conv(w2_hwio, wpack_scratch + BF_WPACK_FLOATS, 0, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_zero(wpack_scratch + 2 * BF_WPACK_FLOATS, 64, s) != hipSuccess) return BF_EHIP;
-    FusedBlockArgs fa;
-    fa.zeros = wpack_scratch + 2 * BF_WPACK_FLOATS;
-    fa.in = in; fa.out = out; fa.w1pack = wpack_scratch; fa.w2pack = wpack_scratch + BF_WPACK_FLOATS; fa.scale = scale;
-    fa.shift = shift; fa.B = B; fa.H = H; fa.W = W; fa.tiles_x = fa.tiles_y = fa.ntiles = 0; fa.act1_relu = act1_relu;
-    return bf_launch_fused_block(fa, s) == hipSuccess ? BF_OK : BF_EHIP;
-}
-
-// split-f16 fused block on fp32 NHWC tensors: convert in, run, convert out.  scratch: float buffer of at least
-// 2 * B*H*W*16 + BF_H3_BLOCK_FLOATS + 4608 + 32 + 64 + 128 floats (two split-planar activations, packed weights,
-// the two HWIO kernels + gamma-free BN stand-in, zero line, dump line).
-extern "C" int64_t bf_debug_fused_block_h3_scratch_floats(int B, int H, int W)
-{
-    return 2 * (int64_t)B * H * W * 16 + BF_H3_BLOCK_FLOATS + 4608 + 16 + 32 + 64 + 256;
-}
-
-extern "C" int bf_debug_fused_block_h3(const float* in, const float* w1_hwio, const float* w2_hwio, const float* scale,
-                                       const float* shift, float* out, float* scratch, int B, int H, int W, int act1_relu,
-                                       void* stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t act = (int64_t)B * H * W * 16;
-    float* xa = scratch;
-    float* ya = scratch + act;
-    float* pk = ya + act;                          // BF_H3_BLOCK_FLOATS
-    float* params = pk + BF_H3_BLOCK_FLOATS;       // [w1 2304][w2 2304][gamma 16]
-    float* state = params + 4608 + 16;             // [mean 16][var 16]
-    float* zeros = state + 32;                     // 64
-    float* dump = zeros + 64;                      // 256
-    // the caller's scale / shift stand in for the folded BN (ext_scale / ext_shift of the pack kernel)
-    if (hipMemcpyAsync(params, w1_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (hipMemcpyAsync(params + 2304, w2_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_zero(zeros, 64, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_pack_h3(params, state, 0, 4608 + 16, pk, BF_H3_BLOCK_FLOATS, 1, 0, 0.f, scale, shift, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_h3_from_f32(in, xa, B, H, W, s) != hipSuccess) return BF_EHIP;
-    FusedH3Args fa;
-    fa.in = xa; fa.out = ya; fa.aux = pk;
-    fa.w1r = fa.aux + 64; fa.w2r = fa.aux + 64 + BF_H3R_WPACK_FLOATS;
-    fa.B = B; fa.H = H; fa.W = W; fa.tiles_x = fa.tiles_y = fa.ntiles = 0; fa.rows_per_tile = 0; fa.variant = -1; fa.reverse_tiles = 0; fa.act1_relu = act1_relu;
-    fa.zeros = zeros; fa.dump = dump; fa.dbg = g_fused_dbg;
-    fa.head_wh = nullptr; fa.head_out = nullptr; fa.head_u8 = 0; fa.Ho = fa.Wo = 0; fa.denormalize = 0; fa.v_min = fa.v_max = 0.f;
-    fa.status = nullptr;
-    if (bf_launch_fused_block_h3(fa, s) != hipSuccess) return BF_EHIP;
-    return bf_launch_h3_to_f32(ya, out, B, H, W, s) == hipSuccess ? BF_OK : BF_EHIP;
-}
-
-// TWO split-f16 fused blocks in one launch (fused_h3w.hip) on fp32 NHWC tensors: convert in, run, convert out.
-// w_hwio = [4][3][3][16][16] (conv1a, conv2a, conv1b, conv2b), scale / shift = [2][16] (block a, b).
-extern "C" int64_t bf_debug_fused_block2_h3_scratch_floats(int B, int H, int W)
-{
-    return 2 * (int64_t)B * H * W * 16 + 2 * (int64_t)BF_H3_BLOCK_FLOATS + 2 * (4608 + 16) + 32 + 64;
-}
-
-extern "C" int bf_debug_fused_block2_h3(const float* in, const float* w_hwio, const float* scale, const float* shift, float* out,
-                                        float* scratch, int B, int H, int W, int act1_relu, int reverse, void* stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    if (!in || !w_hwio || !scale || !shift || !out || !scratch || B <= 0 || H <= 0 || W <= 0) return BF_EINVAL;
-    const int64_t act = (int64_t)B * H * W * 16;
-    float* xa = scratch;
-    float* ya = scratch + act;
-    float* pk = ya + act;                              // 2 x BF_H3_BLOCK_FLOATS
-    float* params = pk + 2 * BF_H3_BLOCK_FLOATS;       // 2 x [w1 2304][w2 2304][gamma 16]
-    float* state = params + 2 * (4608 + 16);           // [mean 16][var 16] (unused: the caller's scale / shift stand in)
-    float* zeros = state + 32;                         // 64
-    if (hipMemcpyAsync(params, w_hwio, 4608 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (hipMemcpyAsync(params + 4608 + 16, w_hwio + 4608, 4608 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_zero(zeros, 64, s) != hipSuccess) return BF_EHIP;
-    for (int b = 0; b < 2; ++b)
-        if (bf_launch_pack_h3(params + b * (4608 + 16), state, 0, 4608 + 16, pk + b * BF_H3_BLOCK_FLOATS, BF_H3_BLOCK_FLOATS, 1, 0,
-                              0.f, scale + 16 * b, shift + 16 * b, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_h3_from_f32(in, xa, B, H, W, s) != hipSuccess) return BF_EHIP;
-    FusedH3WArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.in = xa; fa.out = ya;
-    for (int b = 0; b < 2; ++b) {
-        const float* aux = pk + b * BF_H3_BLOCK_FLOATS;
-        fa.aux[b] = aux; fa.w1r[b] = aux + 64; fa.w2r[b] = aux + 64 + BF_H3R_WPACK_FLOATS;
-    }
-    fa.B = B; fa.H = H; fa.W = W; fa.reverse_tiles = reverse ? 1 : 0; fa.act1_relu = act1_relu;
-    fa.zeros = zeros; fa.dbg = g_fused_dbg;
-    if (bf_launch_fused_block2_h3w(fa, s) != hipSuccess) return BF_EHIP;
-    return bf_launch_h3_to_f32(ya, out, B, H, W, s) == hipSuccess ? BF_OK : BF_EHIP;
-}
-
-extern "C" int bf_debug_set_h3_variant(int variant)
-{
-    bf_set_h3_variant(variant);
-    return BF_OK;
-}
-
-// single split-f16 3x3 convolution on fp32 NHWC (the training convolution); scratch = 4 * BF_H3_TRAIN_PACK floats + 2304
-extern "C" int64_t bf_debug_conv3x3_h3_scratch_floats(void) { return 4 * (int64_t)BF_H3_TRAIN_PACK_FLOATS + 2 * 2304 + 16; }
-extern "C" int bf_debug_conv3x3_h3(const float* in, const float* w_hwio, float* out, const float* res, const float* mask,
-                                   float* stats, float* scratch, int B, int H, int W, int epi, int transpose_flip, void* stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    float* params = scratch + 4 * BF_H3_TRAIN_PACK_FLOATS;        // [w 2304][unused 2304][gamma 16]: one "layer"
-    if (hipMemcpyAsync(params, w_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (hipMemcpyAsync(params + 2304, w_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_pack_h3_train(params, 0, 4608 + 16, scratch, 1, 2, 2320, s) != hipSuccess) return BF_EHIP;
-    ConvArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.in = in; ca.out = out; ca.wpack = scratch + (transpose_flip ? 2 : 0) * BF_H3_TRAIN_PACK_FLOATS;
-    ca.res = res; ca.mask = mask; ca.stats = stats; ca.B = B; ca.H = H; ca.W = W;
-    return bf_launch_conv3x3_h3(ca, epi, s) == hipSuccess ? BF_OK : BF_EHIP;
-}
-
-// conv3x3_h3 with "affine + add on load": y = in + pre_scale * pre_c + pre_shift -> pre_out ; out = [relu] conv(y)
-extern "C" int bf_debug_conv3x3_h3_pre(const float* in, const float* pre_c, const float* pre_scale, const float* pre_shift,
-                                       float* pre_out, const float* w_hwio, float* out, float* scratch, int B, int H, int W, int relu,
-                                       int reverse, void* stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    float* params = scratch + 4 * BF_H3_TRAIN_PACK_FLOATS;
-    if (hipMemcpyAsync(params, w_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (hipMemcpyAsync(params + 2304, w_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_pack_h3_train(params, 0, 4608 + 16, scratch, 1, 2, 2320, s) != hipSuccess) return BF_EHIP;
-    ConvArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.in = in; ca.out = out; ca.wpack = scratch; ca.B = B; ca.H = H; ca.W = W; ca.reverse = reverse;
-    ca.pre_c = pre_c; ca.pre_scale = pre_scale; ca.pre_shift = pre_shift; ca.pre_out = pre_out;
-    return bf_launch_conv3x3_h3(ca, relu ? EPI_RELU : 0, s) == hipSuccess ? BF_OK : BF_EHIP;
-}
-
-// the training-mode forward of one [3,3] block in one kernel (train_fwd_h3t.hip): a_out = x + pre_scale * pre_c + pre_shift (pre_c
-// given), t_out = [relu] conv_0(a) (t_out given), c_out = conv_1(t), stats[32] = per-channel sum | sum of squares of c_out.
-// scratch: bf_debug_fwd_block_h3t_scratch_floats(B, H, W) floats
-extern "C" int64_t bf_debug_fwd_block_h3t_scratch_floats(int B, int H, int W)
-{
-    return 4 * (int64_t)BF_H3_TRAIN_PACK_FLOATS + 2 * 2304 + 16 + (int64_t)bf_fwd_block_h3t_grid(B, H, W) * 32;
-}
-extern "C" int bf_debug_fwd_block_h3t(const float* x, const float* pre_c, const float* pre_scale, const float* pre_shift,
-                                      const float* w0_hwio, const float* w1_hwio, float* a_out, float* t_out, float* c_out, float* stats,
-                                      float* scratch, int B, int H, int W, int relu, int reverse, void* stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    if (!bf_fwd_block_h3t_supports(H, W)) return BF_EUNSUPPORTED;
-    float* params = scratch + 4 * BF_H3_TRAIN_PACK_FLOATS;
-    if (hipMemcpyAsync(params, w0_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (hipMemcpyAsync(params + 2304, w1_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_pack_h3_train(params, 0, 4608 + 16, scratch, 1, 2, 2320, s) != hipSuccess) return BF_EHIP;
-    float* partial = params + 2 * 2304 + 16;
-    FwdBlockH3Args fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.x = x; fa.pre_c = pre_c; fa.pre_scale = pre_scale; fa.pre_shift = pre_shift; fa.a_out = a_out; fa.t_out = t_out; fa.c_out = c_out;
-    fa.wpack0 = scratch; fa.wpack1 = scratch + BF_H3_TRAIN_PACK_FLOATS; fa.stats = partial;
-    fa.B = B; fa.H = H; fa.W = W; fa.reverse = reverse; fa.act_relu = relu;
-    if (bf_launch_fwd_block_h3t(fa, s) != hipSuccess) return BF_EHIP;
-    return bf_launch_reduce_partials(partial, bf_fwd_block_h3t_grid(B, H, W), 32, stats, 1.0f, s) == hipSuccess ? BF_OK : BF_EHIP;
-}
-
-// the backward of one [3,3] block in one kernel with T recomputed (train_bwd_h3t.hip): dc = k1 g + k2 c + k3 (coef = k1 | k2 | k3),
-// T = [relu] conv_0(a), dw1 = T^T dc, dT = dgrad_1(dc) [* (T > 0)], dw0 = a^T dT, out = dgrad_0(dT) + g, stats[32] = sums of out |
-// out * bnc (bnc given).  scratch: bf_debug_bwd_block_h3t_scratch_floats(B, H, W) floats
-extern "C" int64_t bf_debug_bwd_block_h3t_scratch_floats(int B, int H, int W)
-{
-    return 4 * (int64_t)BF_H3_TRAIN_PACK_FLOATS + 2 * 2304 + 16 + (int64_t)bf_bwd_block_h3t_grid(B, H, W) * (2 * 2304 + 32);
-}
-extern "C" int bf_debug_bwd_block_h3t(const float* a_in, const float* g, const float* c, const float* coef, const float* w0_hwio,
-                                      const float* w1_hwio, const float* bnc, float* out, float* dw1, float* dw0, float* stats,
-                                      float* scratch, int B, int H, int W, int relu, int reverse, void* stream)
-{
-    // reverse: bit 0 = walk the bands bottom-up; bit 1 = the KERNEL ALONE (weights packed by an earlier call with the same scratch, no
-    // reduction of the partials: bench.py's live timing of the launch)
-    hipStream_t s = (hipStream_t)stream;
-    if (!bf_bwd_block_h3t_supports(H, W)) return BF_EUNSUPPORTED;
-    const bool alone = (reverse & 2) != 0;
-    reverse &= 1;
-    float* params = scratch + 4 * BF_H3_TRAIN_PACK_FLOATS;
-    if (!alone) {
-        if (hipMemcpyAsync(params, w0_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-        if (hipMemcpyAsync(params + 2304, w1_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-        if (bf_launch_pack_h3_train(params, 0, 4608 + 16, scratch, 1, 2, 2320, s) != hipSuccess) return BF_EHIP;
-    }
-    const int grid = bf_bwd_block_h3t_grid(B, H, W);
-    float* wp1 = params + 2 * 2304 + 16;
-    float* wp0 = wp1 + (int64_t)grid * 2304;
-    float* st = wp0 + (int64_t)grid * 2304;
-    BwdBlockH3Args fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.a = a_in; fa.g = g; fa.c = c; fa.coef = coef; fa.bnc = bnc; fa.out = out;
-    fa.wfwd0 = scratch; fa.wdg0 = scratch + 2 * BF_H3_TRAIN_PACK_FLOATS; fa.wdg1 = scratch + 3 * BF_H3_TRAIN_PACK_FLOATS;
-    fa.wpartial1 = wp1; fa.wpartial0 = wp0; fa.stats = st;
-    fa.B = B; fa.H = H; fa.W = W; fa.reverse = reverse; fa.act_relu = relu; fa.dbg = g_fused_dbg;
-    if (bf_launch_bwd_block_h3t(fa, s) != hipSuccess) return BF_EHIP;
-    if (alone) return BF_OK;
-    if (bf_launch_reduce_partials(wp1, grid, 2304, dw1, 1.0f, s) != hipSuccess) return BF_EHIP;
-    if (bf_launch_reduce_partials(wp0, grid, 2304, dw0, 1.0f, s) != hipSuccess) return BF_EHIP;
-    if (bnc && stats && bf_launch_reduce_partials(st, grid, 32, stats, 1.0f, s) != hipSuccess) return BF_EHIP;
-    return BF_OK;
-}
-
-// the fused backward kernel of one convolution (train_bwd_h3.hip): dw = x^T g', dx = dgrad(g') [* (x > 0) | + res], with
-// g' = k1 g + k2 c + k3 when coef is given; stats (EPI_BNBWD): [grid][32] partials of (sum dx, sum dx * bnc).
-// scratch: bf_debug_bwd3x3_h3_scratch_floats(B, H, W) floats
-extern "C" int64_t bf_debug_bwd3x3_h3_scratch_floats(int B, int H, int W)
-{
-    return bf_debug_conv3x3_h3_scratch_floats() + (int64_t)bf_bwd3x3_h3_grid(B, H, W) * (2304 + 32);
-}
-extern "C" int bf_debug_bwd3x3_h3_grid(int B, int H, int W) { return bf_bwd3x3_h3_grid(B, H, W); }
-extern "C" int bf_debug_bwd3x3_h3_grid_ex(int B, int H, int W, int dbuf) { return bf_bwd3x3_h3_grid_ex(B, H, W, dbuf); }
-extern "C" int bf_debug_bwd3x3_h3(const float* x, const float* g, const float* c, const float* coef, const float* w_hwio, float* out,
-                                  const float* res, const float* bnc, float* dw, float* stats, float* scratch, int B, int H, int W,
-                                  int epi, int reverse, int repack, void* stream)
-{
-    hipStream_t s = (hipStream_t)stream;
-    if (repack) {
-        float* params = scratch + 4 * BF_H3_TRAIN_PACK_FLOATS;
-        if (hipMemcpyAsync(params, w_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-        if (hipMemcpyAsync(params + 2304, w_hwio, 2304 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return BF_EHIP;
-        if (bf_launch_pack_h3_train(params, 0, 4608 + 16, scratch, 1, 2, 2320, s) != hipSuccess) return BF_EHIP;
-    }
-    float* partial = scratch + bf_debug_conv3x3_h3_scratch_floats();
-    BwdH3Args a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.g = g; a.c = c; a.coef = coef; a.wpack = scratch + 2 * BF_H3_TRAIN_PACK_FLOATS; a.out = out; a.res = res; a.bnc = bnc;
-    a.wpartial = partial; a.stats = partial + (int64_t)bf_bwd3x3_h3_grid(B, H, W) * 2304;
-    a.B = B; a.H = H; a.W = W; a.reverse = reverse & 1; a.dbuf = (reverse >> 1) & 1;       // reverse: bit 0 walk direction, bit 1 kernel form
-    if (bf_launch_bwd3x3_h3(a, epi, dw, s) != hipSuccess) return BF_EHIP;
-    if (stats && (epi & EPI_BNBWD) &&
-        hipMemcpyAsync(stats, a.stats, (size_t)bf_bwd3x3_h3_grid_ex(B, H, W, a.dbuf) * 32 * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return BF_EHIP;
-    return BF_OK;
-}
-
-extern "C" int64_t bf_debug_wgrad_partial_floats(int B, int H, int W) { return (int64_t)bf_wgrad_grid(B, H, W) * 2304; }
-
-extern "C" int bf_debug_wgrad3x3_h3(const float* x, const float* dy, float* partial, float* dw, int B, int H, int W, void* stream)
-{
-    return bf_launch_wgrad3x3_h3(x, dy, partial, dw, B, H, W, (hipStream_t)stream) == hipSuccess ? BF_OK : BF_EHIP;
-}
-
-extern "C" int bf_debug_wgrad3x3(const float* x, const float* dy, float* partial, float* dw, int B, int H, int W, void* stream)
-{
-    return bf_launch_wgrad3x3_c16(x, dy, partial, dw, B, H, W, (hipStream_t)stream) == hipSuccess ? BF_OK : BF_EHIP;
-}
-
-// raw MFMA layout probe: D = A(16x4) * B(4x16) with A[m][k] = a_in[m*4+k], B[k][n] = b_in[k*16+n]
-__global__ void mfma_probe_kernel(const float* a_in, const float* b_in, float* d_out)
-{
-    const int l = threadIdx.x;
-    const float a = a_in[(l & 15) * 4 + (l >> 4)];
-    const float b = b_in[(l >> 4) * 16 + (l & 15)];
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) d_out[((l >> 4) * 4 + j) * 16 + (l & 15)] = acc[j];
-}
-
-extern "C" int bf_debug_mfma_probe(const float* a, const float* b, float* d, void* stream)
-{
-    hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a, b, d);
-    return hipGetLastError() == hipSuccess ? BF_OK : BF_EHIP;
 }

@@ -586,8 +586,9 @@ int bf_op_axpy(float* y, const float* x, float a, int overwrite, int64_t n, void
  *   f16 matrix cores; 0: exact fp32.  With it (all default 1, A/B only): "train_fused_bwd" = weight gradient, data gradient
  *   and the BatchNorm-backward apply of a convolution in one kernel; "train_fused_fwd" = a block's BatchNorm apply + skip Add
  *   formed by the next block's first convolution while it stages its tile; "train_zigzag" = consecutive tile kernels walk the
- *   tensors in opposite directions (Infinity Cache reuse).  "train_fused_bwd2" (default 0): [3,3] blocks with BatchNorm and
- *   ReLU run BOTH convolutions' backward in one kernel (6 tensor passes for 9; measured slower than the two kernels).
+ *   tensors in opposite directions (Infinity Cache reuse).  "train_fused_bwd2" and "train_bwd_dbuf" selected two backward kernels that
+ *   measured slower than the ones they were to replace and have been removed: both names are accepted for every
+ *   value and change nothing ("train_bwd_block" is the one-kernel-per-block backward).
  * "fused_head" = 1: with split-f16 blocks, a linear denoiser head and 3 output channels, the head (premultiplied 16 x 3
  *   matrix, tanh, denormalise, rounding) runs in the epilogue of the last block: no head kernel, the last block output is
  *   never written; 0 (default): separate head kernel (the two measure within 0.5 % of each other).

@@ -68,7 +68,9 @@ int bf_debug_bwd_block_h3t(const float* a, const float* g, const float* c, const
                            int width, int relu, int reverse, void* stream);
 int64_t bf_debug_bwd3x3_h3_scratch_floats(int batch, int height, int width);
 int bf_debug_bwd3x3_h3_grid(int batch, int height, int width);
-int bf_debug_bwd3x3_h3_grid_ex(int batch, int height, int width, int dbuf);    /* partial rows written; `reverse` bit 1 of the call below = dbuf */
+/* dbuf selected a double-buffered form of the kernel that has been removed: _grid_ex returns bf_debug_bwd3x3_h3_grid for every dbuf, and
+   bit 1 of `reverse` in the call below (the same switch) is accepted and ignored; bit 0 = walk the tiles from the last to the first */
+int bf_debug_bwd3x3_h3_grid_ex(int batch, int height, int width, int dbuf);
 int bf_debug_bwd3x3_h3(const float* x, const float* g, const float* c, const float* coef, const float* w_hwio, float* out,
                        const float* res, const float* bnc, float* dw, float* stats, float* scratch, int batch, int height,
                        int width, int epi, int reverse, int repack, void* stream);

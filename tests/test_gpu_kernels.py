@@ -334,11 +334,13 @@ def test_wgrad3x3(shape, h3):
 BWD_SHAPES = SHAPES + [(24, 128, 160)]          # the last one: more tiles (1200) than persistent workgroups (512)
 
 
+# dbuf = 1 asked for the 512-thread double-buffered form of the kernel, which lost its A/B and was removed: the bit is
+# accepted and ignored, so the "dbuf" ids run the one kernel there is against the same oracle and bars
 @pytest.mark.parametrize("dbuf", [0, 1], ids=["2wg", "dbuf"])
 @pytest.mark.parametrize("shape", BWD_SHAPES)
 @pytest.mark.parametrize("reverse", [0, 1])
 def test_bwd3x3_h3_second_convolution(shape, reverse, dbuf):
-    """BatchNorm-backward apply on load + weight gradient + masked data gradient (a block's convolution j >= 1)."""
+    """BatchNorm-backward apply on load + weight gradient + masked data gradient (a block's convolution j >= 1); dbuf: ignored bit."""
     B, H, W = shape
     x = np.maximum(_rand((B, H, W, 16), 40), 0)                       # activated input: also the mask
     g, c = _rand((B, H, W, 16), 41), _rand((B, H, W, 16), 42)
@@ -355,10 +357,10 @@ def test_bwd3x3_h3_second_convolution(shape, reverse, dbuf):
     assert_close(dw0, ref_dw, rel=3e-6 * np.sqrt(B * H * W), what=f"dw plain {shape}")
 
 
-@pytest.mark.parametrize("dbuf", [0, 1], ids=["2wg", "dbuf"])
+@pytest.mark.parametrize("dbuf", [0, 1], ids=["2wg", "dbuf"])          # "dbuf": the ignored bit (see above), same kernel
 @pytest.mark.parametrize("shape", BWD_SHAPES)
 def test_bwd3x3_h3_first_convolution(shape, dbuf):
-    """weight gradient + data gradient + skip gradient, and the sums the BatchNorm backward of the block in front needs."""
+    """weight gradient + data gradient + skip gradient, and the sums the BatchNorm backward of the block in front needs; dbuf: ignored bit."""
     B, H, W = shape
     x, g = _rand((B, H, W, 16), 50), _rand((B, H, W, 16), 51)
     res, bnc = _rand((B, H, W, 16), 52), _rand((B, H, W, 16), 53)
@@ -374,6 +376,23 @@ def test_bwd3x3_h3_first_convolution(shape, dbuf):
     assert_close(tot[16:], (ref_dx * bnc).sum(axis=(0, 1, 2)), rel=1e-5 * np.sqrt(ref_dx.size), what="sum dx * c")
     dx1, dw1 = bwd3x3_h3_gpu(x, g, w, N.EPI_RES, res=res, dbuf=dbuf)
     assert np.array_equal(dx1, dx) and np.array_equal(dw1, dw)
+
+
+def test_bwd3x3_h3_dbuf_bit_is_ignored():
+    """bit 1 of `reverse` (dbuf) selected the removed double-buffered kernel: the call runs the same kernel and gives the same bits --
+    dx, dw and the per-workgroup sums, whose row count no longer depends on the bit (2 x 2 ragged tiles of 16 x 32)"""
+    B, H, W = 2, 24, 40
+    x, g = np.maximum(_rand((B, H, W, 16), 70), 0), _rand((B, H, W, 16), 71)
+    res, bnc, c = _rand((B, H, W, 16), 72), _rand((B, H, W, 16), 73), _rand((B, H, W, 16), 74)
+    w = _rand((3, 3, 16, 16), 75) * 0.1
+    coef = np.concatenate([1 + 0.3 * _rand(16, 76), 0.2 * _rand(16, 77), 0.1 * _rand(16, 78)]).astype(np.float32)
+    first = [bwd3x3_h3_gpu(x, g, w, N.EPI_RES | N.EPI_BNBWD, res=res, bnc=bnc, dbuf=d) for d in (0, 1)]
+    assert first[0][2].shape == first[1][2].shape
+    for a, b in zip(first[0], first[1]):
+        assert np.array_equal(a, b)
+    second = [bwd3x3_h3_gpu(x, g, w, N.EPI_MASK, c=c, coef=coef, dbuf=d) for d in (0, 1)]
+    for a, b in zip(second[0], second[1]):
+        assert np.array_equal(a, b)
 
 
 def test_bwd3x3_h3_exact_on_integers_and_deterministic():

@@ -67,8 +67,9 @@ def test_train_step_matches_oracle(no_layers, shape, train_arith):
 
 @pytest.mark.parametrize("no_layers,shape", [(1, (2, 16, 32)), (3, (3, 33, 47)), (2, (5, 70, 150))])
 def test_two_convolution_backward_kernel_matches_oracle_and_the_two_kernel_path(no_layers, shape):
-    """train_fused_bwd2 = 1 (bwd2_h3_kernel: both convolutions' backward of a block in one launch, dT never leaves the CU):
-    the same oracle bars as the default path, and the two paths agree with each other far inside those bars."""
+    """train_fused_bwd2 = 1 asked for bwd2_h3_kernel (both convolutions' backward of a block in one launch).  That kernel lost its
+    A/B and was removed; the option is still accepted and changes nothing, so this now runs the default backward
+    twice: the same oracle bars as before, and the two runs agree with each other far inside those bars."""
     cfg, spec, ls, params, state, m, fns = _setup(no_layers)
     clean, noisy = O.synthetic_batch(*shape, seed=23)
     gt, x = clean.astype(np.float32), noisy.astype(np.float32)
@@ -83,6 +84,41 @@ def test_two_convolution_backward_kernel_matches_oracle_and_the_two_kernel_path(
     _cmp_grads(spec, got[1][1], r_grads)
     assert got[0][0] == got[1][0]                                        # same forward
     _cmp_grads(spec, got[1][1], got[0][1], rel=5e-5)
+
+
+def _step_bits(m, fns, params, state, gt, x, opts):
+    """one training step from the given weights with the given options: (loss, gradients, moving statistics, kernel names)"""
+    m.set_weights(params, state)
+    for k, v in opts.items():
+        m.set_option(k, v)
+    total, ml, dl, pred, grads = fns.train_step_single_gpu(torch.from_numpy(gt), torch.from_numpy(x), (1.0,), 0.0, None)
+    return total.item(), grads.cpu().numpy().copy(), m.state.cpu().numpy().copy(), N.lib().bf_get_train_kernels(m._h).decode()
+
+
+def test_retired_backward_options_are_no_ops():
+    """train_fused_bwd2 and train_bwd_dbuf selected kernels that were removed.  Both names are still accepted; neither
+    changes a launch: loss, every gradient tensor and the moving statistics are the SAME BITS as with both at 0 (the kernels sum in
+    a fixed order), on the per-convolution backward kernel (2 x 2 ragged 16 x 32 tiles) and on the block backward kernel."""
+    cfg, spec, ls, params, state, m, fns = _setup(2)
+    clean, noisy = O.synthetic_batch(2, 24, 40, seed=61)
+    gt, x = clean.astype(np.float32), noisy.astype(np.float32)
+
+    def same_bits(got, base):
+        assert got[0] == base[0]
+        for name, (o, s) in spec.offsets().items():
+            n = int(np.prod(s))
+            assert np.array_equal(got[1][o:o + n], base[1][o:o + n]), name
+        assert np.array_equal(got[2], base[2])
+
+    for bwd_block, kernel, combos in ((0, "bwd3x3_h3_kernel", [(1, 0), (0, 1), (1, 1)]), (2, "bwd_block_h3t_kernel", [(1, 1)])):
+        base = None
+        for bwd2, dbuf in [(0, 0)] + combos:
+            got = _step_bits(m, fns, params, state, gt, x, {"train_bwd_block": bwd_block, "train_fused_bwd2": bwd2, "train_bwd_dbuf": dbuf})
+            assert kernel in got[3] and "bwd2_h3_kernel" not in got[3], got[3]
+            if base is None:
+                base = got
+            else:
+                same_bits(got, base)
 
 
 @pytest.mark.parametrize("no_layers,shape", [(1, (2, 16, 32)), (3, (3, 33, 47)), (2, (5, 70, 150)), (4, (2, 40, 256))])
@@ -686,8 +722,9 @@ def test_the_engine_learns_to_denoise(tmp_path):
 def test_random_training_configurations_and_options_match_oracle(seed):
     """a seeded sweep over the engine's training path: depth, base kernel size, 1 / 2 / 3 convolutions per block, BatchNorm on / off, the
     three loss terms and the hinge, ragged shapes, and every set_option switch of the training step (arithmetic of the convolutions,
-    fused forward / backward kernels, double-buffered backward, tile order): loss, prediction, every gradient tensor and the moving
-    statistics against the oracle"""
+    fused forward / backward kernels, tile order): loss, prediction, every gradient tensor and the moving statistics against the
+    oracle.  The retired train_fused_bwd2 / train_bwd_dbuf are still drawn and set (accepted, ignored): every seed keeps its
+    model, shape and remaining options"""
     rng = np.random.default_rng(11000 + seed)
     nb = int(rng.choice([1, 2, 2, 2, 3]))
     cfg = O.canonical_config(no_layers=int(rng.integers(1, 5)), kernel_size=int(rng.choice([1, 3, 5, 7])))
