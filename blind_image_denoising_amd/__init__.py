@@ -32,6 +32,8 @@ from .file_operations import load_image
 from . import metrics
 from .metrics import ImageMetrics, image_metrics, image_metric_sums, psnr, ssim, mae, evaluate
 from . import regularizers
+from . import pruning
+from .pruning import (PruneStrategy, prune_function_builder, get_conv2d_weights, conv2d_sparsity, conv2d_ranges)
 from .custom_layers import RandomOnOff, Multiplier, ChannelwiseMultiplier
 
 current_dir = pathlib.Path(__file__).parent.resolve()

@@ -9,20 +9,7 @@
 // the result does not depend on the launch geometry and a numpy restatement (oracle/bfcnn_oracle.py) can follow it.
 // HBM-bound: reads 4 B, writes 8 B per element.
 #include "bf_common.h"
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+#include "philox.h"
 
 // first standard normal with |z| <= 2 of the element's stream (Box-Muller on successive Philox outputs)
 __device__ __forceinline__ float truncated_normal(uint32_t idx_lo, uint32_t idx_hi, uint32_t stream, uint32_t k0, uint32_t k1)
