@@ -19,6 +19,7 @@ from .utilities import load_config, save_config, input_shape_fixer
 from .model import (BuilderResults, HydraModel, model_builder, describe_resnet, save_model, load_hydra,
                     build_normalize_model, build_denormalize_model)
 from .module_denoiser import DenoiserModule, GraphedDenoiserModule
+from .self_ensemble import SelfEnsembleDenoiserModule
 from .loss import loss_function_builder
 from .optimizer import optimizer_builder, schedule_builder, deep_supervision_schedule_builder
 from .train_loop import (train_loop, build_train_functions, DataParallelTrainer, NativeCommunicator, shard_batch,
@@ -72,10 +73,17 @@ if pretrained_dir.is_dir():
         }
 
 
-def load_model(model_path: str, device=None) -> DenoiserModule:
+def load_model(model_path: str, device=None, self_ensemble=None):
     """bfcnn/__init__.py:81-97: a registry name, a model directory (pipeline.json + weights.npz written by
     `save_model`), or a `.keras` archive of a trained unet_laplacian hydra / the directory holding `model_hydra.keras`
-    (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]."""
+    (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]: a
+    DenoiserModule, or with `self_ensemble` = "d4", "flips" or a sequence of transform numbers 0..7 that module wrapped in a
+    SelfEnsembleDenoiserModule (the mean over the flips and rotations of the image; self_ensemble.py)."""
+    module = _load_module(model_path, device)
+    return module if self_ensemble is None else SelfEnsembleDenoiserModule(module, transforms=self_ensemble)
+
+
+def _load_module(model_path: str, device=None) -> DenoiserModule:
     # --- argument checking
     if model_path is None or len(model_path) <= 0:
         raise ValueError("model_path cannot be empty")

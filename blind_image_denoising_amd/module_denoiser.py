@@ -96,8 +96,8 @@ class DenoiserModule:
         hydra.set_option("arith", 0)
         return False
 
-    def __call__(self, image):
-        """image: uint8 tensor of rank 4 (the input_signature of module_denoiser.py:43-45)."""
+    def _checked_input(self, image):
+        """the argument checks of a call: (image as a uint8 [B,H,W,C] torch tensor, whether a numpy array was given)"""
         was_numpy = isinstance(image, np.ndarray)
         if was_numpy:
             image = torch.from_numpy(np.ascontiguousarray(image))
@@ -109,9 +109,19 @@ class DenoiserModule:
         hydra = self._model_hydra
         if image.shape[-1] != hydra.desc.in_channels:
             raise ValueError(f"expected {hydra.desc.in_channels} channels, got {image.shape[-1]}")
+        return image, was_numpy
+
+    def _empty_output(self, image: torch.Tensor, was_numpy: bool):
+        """what a call returns for a batch of no images"""
+        out = torch.empty((0,) + tuple(image.shape[1:3]) + (self._model_hydra.desc.out_channels,), dtype=torch.uint8)
+        return out.numpy() if was_numpy else out
+
+    def __call__(self, image):
+        """image: uint8 tensor of rank 4 (the input_signature of module_denoiser.py:43-45)."""
+        image, was_numpy = self._checked_input(image)
+        hydra = self._model_hydra
         if image.shape[0] == 0:
-            out = torch.empty((0,) + tuple(image.shape[1:3]) + (hydra.desc.out_channels,), dtype=torch.uint8)
-            return out.numpy() if was_numpy else out
+            return self._empty_output(image, was_numpy)
         hydra._require_gpu()
         self.check_status(wait=False)          # the previous device-tensor call, if its status has arrived by now
         image = image.to(hydra.device).contiguous()
