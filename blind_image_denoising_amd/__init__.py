@@ -32,6 +32,7 @@ from .export_model import export_model
 from .file_operations import load_image
 from . import metrics
 from .metrics import ImageMetrics, image_metrics, image_metric_sums, psnr, ssim, mae, evaluate
+from .noise_estimate import NoiseEstimate, noise_statistics, noise_summary, estimate_noise, evaluate_blind
 from . import regularizers
 from . import pruning
 from .pruning import (PruneStrategy, prune_function_builder, get_conv2d_weights, conv2d_sparsity, conv2d_ranges)

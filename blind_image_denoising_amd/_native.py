@@ -72,6 +72,8 @@ SIGNATURES = {
     "bf_noise_augment": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, C.c_uint64, _P]),
     "bf_image_metrics_scratch_bytes": (_I64, [_I, _I, _I, _I, _I]),
     "bf_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _D, _D, _D, _P, _P, _I64, _P]),
+    "bf_noise_estimate_scratch_bytes": (_I64, [_I, _I, _I, _I]),
+    "bf_noise_estimate": (_I, [_P, _I, _I, _I, _I, _I, _P, _I64, _P, _P]),
     "bf_op_pack_pointwise": (_I, [_P, _P, _I, _I, _P]),
     "bf_op_pointwise": (_I, [_P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _F, _P]),
     "bf_op_pointwise_ex": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _F, _I, _P]),

@@ -1,0 +1,228 @@
+// No-reference noise statistics of one NHWC batch (uint8 or float32) in one pass, per image and channel:
+//   S  = sum |L| over the (H-2)(W-2) interior pixels, L = x (*) [[1,-2,1],[-2,4,-2],[1,-2,1]]   (Immerkaer, "Fast noise variance
+//        estimation", 1996): sigma_fast = sqrt(pi/2) / 6 * S / ((H-2)(W-2));
+//   the 511-bin histogram of q = |x00 - x01 - x10 + x11| over the complete 2x2 cells (uint8 only).  q = 2 |d| for the orthonormal
+//        Haar HH coefficient d, so Donoho's MAD rule reads sigma_mad = median(q) / 2 / 0.6745;
+//   the number of samples equal to 0 or 255 (uint8 only): saturation biases both estimators low.
+// The host side is blind_image_denoising_amd/noise_estimate.py; the formulas and the exactness argument are DESIGN.md 7.7.
+//
+// Layout.  The mask is the outer product of [1,-2,1] with itself: with h(y,x) = x(y,x-1) - 2 x(y,x) + x(y,x+1), L(y,x) = h(y-1,x)
+// - 2 h(y,x) + h(y+1,x).  A workgroup (4 waves) owns a tile of NE_BAND = 32 rows x 64 pixel columns; a wave owns NE_SUB = 8 of
+// those rows and a lane one pixel column.  The lane walks down its column from one row above its wave's rows to one row below,
+// per channel the three samples of a row in hand and the h of the two rows above in registers: a sample comes from HBM once
+// and again from L1 / L2 for the two neighbouring lanes and the halo rows (10 rows read per 8 owned).  The Haar cell of an even
+// pixel column and an even row is formed from the same samples (a wave's rows start on an even row and are 8: a cell never
+// crosses waves), counted in LDS bins with atomicAdd on unsigned and merged into 64-bit global bins with one vector atomic per
+// non-empty bin and workgroup.  The lanes own pixels, not elements, so what a plane contributes does not depend on the number
+// of channels it is interleaved with.
+//
+// Exactness.  uint8: |L| <= 2040 and every count are integers, summed per lane in 32 bits (at most 8 terms) and in 64-bit integers
+// from the wave reduction on: S, the histogram and the clipped count are exact and independent of the order (the atomics add integers).  float32: h, L and the sums are formed in double and
+// reduced in a fixed order (wave shuffle, LDS, per-workgroup partials in scratch, one workgroup per plane): two calls return
+// the same bits, and a plane inside a batch the bits of that plane alone.
+#include "bf_common.h"
+#include <math.h>
+#include <type_traits>
+
+namespace {
+
+constexpr int NE_MAXC = 4;
+constexpr int NE_PX = 64;                 // pixel columns of a tile: one per lane
+constexpr int NE_BAND = 32;               // rows of a tile (a workgroup)
+constexpr int NE_SUB = NE_BAND / 4;       // rows of a wave; even, so that a 2x2 cell stays inside one wave
+constexpr int NE_BINS = 511;              // q of a uint8 cell is an integer in 0..510
+constexpr int NE_BINS_PAD = 512;
+
+struct NeTiles {
+    int x, y;
+    NeTiles(int H, int W) : x((W + NE_PX - 1) / NE_PX), y((H + NE_BAND - 1) / NE_BAND) {}
+    int64_t per_image() const { return (int64_t)x * y; }
+};
+
+// one 8-byte slot of the per-workgroup partials: a 64-bit integer for uint8 images, a double for float32 images
+template <typename T> using NeAcc = typename std::conditional<sizeof(T) == 1, long long, double>::type;
+
+__device__ __forceinline__ int ne_abs(int v) { return v < 0 ? -v : v; }
+__device__ __forceinline__ double ne_abs(double v) { return fabs(v); }
+
+// partial[workgroup][channel][2] = {S, clipped count} of the tile; ghist[image][channel][512] += the tile's histogram (uint8)
+template <typename T>
+__global__ __launch_bounds__(256) void noise_estimate_tile_kernel(const T* __restrict__ img, int H, int W, int C, int tiles_x, int tiles_y,
+                                                                  unsigned long long* __restrict__ ghist, NeAcc<T>* __restrict__ partial)
+{
+    constexpr bool U8 = sizeof(T) == 1;
+    using A = NeAcc<T>;
+    using V = typename std::conditional<U8, int, double>::type;      // per lane: at most 8 terms |L| <= 2040
+    __shared__ unsigned hist[U8 ? NE_MAXC : 1][NE_BINS_PAD];
+    __shared__ A red[4][NE_MAXC][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int t = blockIdx.x;
+    const int tx = t % tiles_x;
+    t /= tiles_x;
+    const int ty = t % tiles_y, b = t / tiles_y;
+    if constexpr (U8) {
+        for (int i = threadIdx.x; i < NE_MAXC * NE_BINS_PAD; i += 256) hist[i / NE_BINS_PAD][i % NE_BINS_PAD] = 0u;
+        __syncthreads();
+    }
+    const int p = tx * NE_PX + lane;                              // this lane's pixel column
+    const int y0 = ty * NE_BAND + wave * NE_SUB, y1 = min(y0 + NE_SUB, H);      // this wave's rows [y0, y1)
+    const bool in = p < W, left = in && p >= 1, right = p + 1 < W;
+    const bool lap_ok = left && right;                            // 1 <= p <= W-2
+    const bool cell_ok = right && !(p & 1);                       // the cell of columns p, p+1 is complete
+    const T* base = img + (int64_t)b * H * W * C;
+    const int64_t e = (int64_t)p * C;
+
+    V s[NE_MAXC], clip[NE_MAXC], h1[NE_MAXC], h2[NE_MAXC], dtop[NE_MAXC];
+#pragma unroll
+    for (int c = 0; c < NE_MAXC; ++c) s[c] = clip[c] = h1[c] = h2[c] = dtop[c] = (V)0;
+
+    if (y0 < H)
+        for (int r = max(y0 - 1, 0); r <= min(y1, H - 1); ++r) {  // every index below is guarded: r < H, p - 1 >= 0, p + 1 < W
+            const T* row = base + (int64_t)r * W * C;
+            const bool own = r >= y0 && r < y1;
+            const bool centre = lap_ok && r - 1 >= y0 && r - 1 >= 1 && r - 1 < y1;    // L centred on row r-1 is this wave's
+#pragma unroll
+            for (int c = 0; c < NE_MAXC; ++c)
+                if (c < C) {
+                    const V xm = left ? (V)row[e - C + c] : (V)0, x0 = in ? (V)row[e + c] : (V)0, xp = right ? (V)row[e + C + c] : (V)0;
+                    const V h = xm - 2 * x0 + xp;
+                    if (centre) s[c] += ne_abs(h2[c] - 2 * h1[c] + h);
+                    h2[c] = h1[c];
+                    h1[c] = h;
+                    if constexpr (U8) {
+                        if (own) {
+                            clip[c] += (in && (x0 == 0 || x0 == 255)) ? 1 : 0;
+                            const V d = x0 - xp;
+                            if (!(r & 1)) dtop[c] = d;                              // y0 is even: row r-1 of an odd r is this wave's too
+                            else if (cell_ok) atomicAdd(&hist[c][ne_abs(dtop[c] - d)], 1u);      // |.| <= 510
+                        }
+                    }
+                }
+        }
+
+#pragma unroll
+    for (int c = 0; c < NE_MAXC; ++c) {
+        A ws = (A)s[c], wc = (A)clip[c];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) { ws += __shfl_xor(ws, m); wc += __shfl_xor(wc, m); }
+        if (lane == 0) { red[wave][c][0] = ws; red[wave][c][1] = wc; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < C * 2) {
+        const int c = threadIdx.x >> 1, j = threadIdx.x & 1;
+        partial[((int64_t)blockIdx.x * C + c) * 2 + j] = (red[0][c][j] + red[1][c][j]) + (red[2][c][j] + red[3][c][j]);
+    }
+    if constexpr (U8) {
+        for (int i = threadIdx.x; i < C * NE_BINS_PAD; i += 256) {
+            const int c = i / NE_BINS_PAD, k = i % NE_BINS_PAD;
+            const unsigned v = hist[c][k];
+            if (v != 0u && k < NE_BINS) atomicAdd(&ghist[((int64_t)b * C + c) * NE_BINS_PAD + k], (unsigned long long)v);
+        }
+    }
+}
+
+// out[image][channel] = {S, sigma_fast, sigma_mad, clipped count}; one workgroup per (image, channel)
+template <typename A>
+__global__ __launch_bounds__(256) void noise_estimate_finalize_kernel(const A* __restrict__ partial, const unsigned long long* __restrict__ ghist,
+                                                                      int C, int64_t tiles, double interior, double fast_scale,
+                                                                      double* __restrict__ out)
+{
+    constexpr bool U8 = std::is_same<A, long long>::value;
+    __shared__ A red[2][256];
+    __shared__ unsigned long long cum[NE_BINS_PAD];
+    const int b = blockIdx.x / C, c = blockIdx.x % C, tid = threadIdx.x;
+    const A* p = partial + (int64_t)b * tiles * C * 2 + c * 2;
+    A acc[2] = {(A)0, (A)0};
+    for (int64_t i = tid; i < tiles; i += 256)
+        for (int j = 0; j < 2; ++j) acc[j] += p[i * C * 2 + j];
+    for (int j = 0; j < 2; ++j) red[j][tid] = acc[j];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st)
+            for (int j = 0; j < 2; ++j) red[j][tid] += red[j][tid + st];
+        __syncthreads();
+    }
+    double* o = out + (int64_t)blockIdx.x * 4;
+    if (tid == 0) {
+        o[0] = (double)red[0][0];
+        o[1] = fast_scale * (double)red[0][0] / interior;
+        o[3] = U8 ? (double)red[1][0] : (double)NAN;
+        if (!U8) o[2] = (double)NAN;
+    }
+    if constexpr (U8) {
+        // grouped-data median of the histogram: inclusive scan of the 512 (padded) bins, two per thread, then the one bin k with
+        // cum(k-1) < n/2 <= cum(k) interpolates: bin 0 covers [0, 1/2), bin k >= 1 covers [k - 1/2, k + 1/2)
+        const unsigned long long* g = ghist + (int64_t)blockIdx.x * NE_BINS_PAD;
+        const unsigned long long hk[2] = {g[tid], g[tid + 256]};
+        cum[tid] = hk[0];
+        cum[tid + 256] = hk[1];
+        __syncthreads();
+        for (int off = 1; off < NE_BINS_PAD; off <<= 1) {
+            unsigned long long v[2];
+            for (int j = 0; j < 2; ++j) {
+                const int i = tid + j * 256;
+                v[j] = cum[i] + (i >= off ? cum[i - off] : 0ull);
+            }
+            __syncthreads();
+            cum[tid] = v[0];
+            cum[tid + 256] = v[1];
+            __syncthreads();
+        }
+        const unsigned long long n = cum[NE_BINS_PAD - 1];
+        const double half = (double)n / 2.0;
+        if (tid == 0 && (n == 0ull || hk[0] == n)) o[2] = 0.0;     // no cell differs from zero: nothing to interpolate
+        if (n != 0ull && g[0] != n)
+            for (int j = 0; j < 2; ++j) {
+                const int k = tid + j * 256;
+                const double before = (double)(cum[k] - hk[j]);
+                if (hk[j] != 0ull && (double)cum[k] >= half && before < half) {
+                    const double lo = k == 0 ? 0.0 : (double)k - 0.5, width = k == 0 ? 0.5 : 1.0;
+                    const double med = lo + width * (half - before) / (double)hk[j];
+                    o[2] = med / 2.0 / 0.6745;
+                }
+            }
+    }
+}
+
+bool ne_shape_ok(int B, int H, int W, int C)
+{
+    if (B <= 0 || C < 1 || C > NE_MAXC || H < 3 || W < 3) return false;
+    return (int64_t)W * C <= INT32_MAX - NE_PX * NE_MAXC && NeTiles(H, W).per_image() * B <= INT32_MAX;
+}
+
+int64_t ne_hist_bytes(int B, int C) { return (int64_t)B * C * NE_BINS_PAD * (int64_t)sizeof(unsigned long long); }
+
+}  // namespace
+
+extern "C" int64_t bf_noise_estimate_scratch_bytes(int B, int H, int W, int C)
+{
+    if (!ne_shape_ok(B, H, W, C)) return BF_EINVAL;
+    return ne_hist_bytes(B, C) + NeTiles(H, W).per_image() * B * C * 2 * (int64_t)sizeof(double);
+}
+
+extern "C" int bf_noise_estimate(const void* img, int dtype, int B, int H, int W, int C, void* scratch, int64_t scratch_bytes, double* out,
+                                 void* stream)
+{
+    if (!img || !out || !scratch || (dtype != BF_DTYPE_U8 && dtype != BF_DTYPE_F32) || !ne_shape_ok(B, H, W, C)) return BF_EINVAL;
+    if (scratch_bytes < bf_noise_estimate_scratch_bytes(B, H, W, C) || ((uintptr_t)scratch | (uintptr_t)out) % 8) return BF_EINVAL;
+    if (dtype == BF_DTYPE_F32 && (uintptr_t)img % 4) return BF_EINVAL;
+    const NeTiles tiles(H, W);
+    unsigned long long* ghist = (unsigned long long*)scratch;
+    void* partial = (char*)scratch + ne_hist_bytes(B, C);
+    const dim3 grid((unsigned)(tiles.per_image() * B));
+    const double interior = (double)(H - 2) * (double)(W - 2), fast_scale = sqrt(M_PI / 2.0) / 6.0;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == BF_DTYPE_U8) {
+        if (hipMemsetAsync(ghist, 0, (size_t)ne_hist_bytes(B, C), s) != hipSuccess) return BF_EHIP;
+        hipLaunchKernelGGL(noise_estimate_tile_kernel<uint8_t>, grid, dim3(256), 0, s, (const uint8_t*)img, H, W, C, tiles.x, tiles.y, ghist,
+                           (long long*)partial);
+        hipLaunchKernelGGL(noise_estimate_finalize_kernel<long long>, dim3(B * C), dim3(256), 0, s, (const long long*)partial, ghist, C,
+                           tiles.per_image(), interior, fast_scale, out);
+    } else {
+        hipLaunchKernelGGL(noise_estimate_tile_kernel<float>, grid, dim3(256), 0, s, (const float*)img, H, W, C, tiles.x, tiles.y, ghist,
+                           (double*)partial);
+        hipLaunchKernelGGL(noise_estimate_finalize_kernel<double>, dim3(B * C), dim3(256), 0, s, (const double*)partial, ghist, C,
+                           tiles.per_image(), interior, fast_scale, out);
+    }
+    return hipGetLastError() == hipSuccess ? BF_OK : BF_EHIP;
+}

@@ -229,6 +229,24 @@ int bf_image_metrics(const void* a, const void* b, int dtype, int batch, int hei
                      int filter_size, double filter_sigma, double k1, double k2, double* out, void* scratch, int64_t scratch_bytes,
                      void* stream);
 
+/* No-reference noise statistics of one NHWC batch (dtype: bf_dtype; csrc/noise_estimate.hip) in one pass, for images that have
+ * no clean counterpart.  out = double[batch][channels][4], per image and channel:
+ *   out[..][0] = S = sum |L| over the (height-2)(width-2) interior pixels, L = image (*) [[1,-2,1],[-2,4,-2],[1,-2,1]]
+ *   out[..][1] = sigma_fast = sqrt(pi/2) / 6 * S / ((height-2)(width-2))                 (Immerkaer 1996)
+ *   out[..][2] = sigma_mad = med / 2 / 0.6745, med = the grouped-data median of q = |x00 - x01 - x10 + x11| over the complete
+ *                2x2 cells (q = twice the modulus of the orthonormal Haar HH coefficient; Donoho's MAD rule).  Bin 0 of the
+ *                511-bin histogram covers [0, 1/2), bin k >= 1 covers [k - 1/2, k + 1/2), the bin that holds the n/2-th of the n
+ *                cells is interpolated linearly; 0 when every cell is zero.  uint8 only: NaN for float32.
+ *   out[..][3] = the number of samples equal to 0 or 255 (saturation biases both estimators low).  uint8 only: NaN for float32.
+ * uint8: S, the histogram and the count are 64-bit integer sums, exact in any order.  float32: L and S in fp64, reduced in a
+ * fixed order.  Either way repeated calls return the same bits, and a plane inside a batch the bits of that plane alone.
+ * height and width >= 3, channels in 1..4.  `scratch`: bf_noise_estimate_scratch_bytes bytes, 8-byte aligned, zeroed by the call
+ * on `stream`; nothing is allocated and nothing synchronises.  BF_EINVAL for NULL, a bad shape or dtype, or short or misaligned
+ * scratch. */
+int64_t bf_noise_estimate_scratch_bytes(int batch, int height, int width, int channels);
+int bf_noise_estimate(const void* img, int dtype, int batch, int height, int width, int channels, void* scratch,
+                      int64_t scratch_bytes, double* out, void* stream);
+
 /* ---- unet_laplacian backbone operators (BASELINE.json configs[4]) ------------------------------
  * What bfcnn/backbone_unet_laplacian.py:281-606 builds from keras layers, as fp32 NHWC device operators; the host
  * (blind_image_denoising_amd/unet_laplacian.py) chains them as the reference builder chains its layers.
