@@ -288,6 +288,7 @@ struct BwdBlockH3Args {
 };
 bool       bf_bwd_block_h3t_supports(int H, int W);
 int        bf_bwd_block_h3t_grid(int B, int H, int W);
+int64_t    bf_bwd_block_h3t_strip_rows(int B, int H, int W);     // B * H * strips of the kernel's own strip width
 hipError_t bf_launch_bwd_block_h3t(const BwdBlockH3Args& a, hipStream_t s);
 int        bf_bwd3x3_h3_grid(int B, int H, int W);                 // partial rows (workgroups) a launch writes
 hipError_t bf_launch_bwd3x3_h3(const BwdH3Args& a, int epi, float* dw, hipStream_t s);

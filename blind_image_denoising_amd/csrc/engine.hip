@@ -424,7 +424,7 @@ static TrainLayout train_layout(bf_handle h, int B, int H, int W)
     pf = max64(pf, 4096 * 32);
     pf = max64(pf, (int64_t)bf_wgrad_grid(B, H, W) * 2304);
     pf = max64(pf, (int64_t)bf_bwd3x3_h3_grid(B, H, W) * (2304 + 32));
-    pf = max64(pf, (int64_t)bf_fwd_block_h3t_grid(B, H, W) * 32);
+    pf = max64(pf, 2 * align_up((int64_t)bf_fwd_block_h3t_grid(B, H, W) * 32, 64));  // two sets of BatchNorm sums in turn (train_forward)
     pf = max64(pf, (int64_t)bf_bwd_block_h3t_grid(B, H, W) * (2304 + 64));           // + two sets of BatchNorm sums in turn
     pf = max64(pf, (int64_t)bf_base_wgrad_grid(B, H, W) * h->n_base);
     pf = max64(pf, (int64_t)bf_head_train_grid(B, H, W) * 80);
@@ -889,9 +889,8 @@ static TrainStep make_train_step(bf_handle h, int B, int H, int W, const TrainLa
     t.fwd_block = t.h3t && h->train_fwd_block && h->train_fused_fwd && t.nb == 2 && d.use_bn && bf_fwd_block_h3t_supports(H, W) &&
                   (h->train_fwd_block == 2 || (int64_t)B * H >= 4096);
     // the whole backward of a block in one kernel that RECOMPUTES T_i from A_i (train_bwd_h3t.hip): same kind of block, any width
-    const int64_t bwd_strips = (W + 127) / 128;
     t.bwd_block = t.h3t && h->train_bwd_block && h->train_fused_bwd && t.nb == 2 && d.use_bn && bf_bwd_block_h3t_supports(H, W) &&
-                  (h->train_bwd_block == 2 || (int64_t)B * H * bwd_strips >= 8192);
+                  (h->train_bwd_block == 2 || bf_bwd_block_h3t_strip_rows(B, H, W) >= 8192);
     t.fused_bwd = t.h3t && h->train_fused_bwd;
     // train_fold_finalize with the block backward kernel: launch i reads the sums launch i + 1 wrote and finalises them in its prologue,
     // so the sums go to two buffers in turn (both behind the weight-gradient slots inside `partial`)
@@ -938,8 +937,8 @@ static int train_forward(TrainStep& t, const float* params, float* state, const 
             // train_fold_finalize: the BatchNorm finalisation of block i - 1 runs in THIS launch's prologue (every workgroup sums that
             // block's partials itself; two partial buffers in turn), so a forward is one launch per block instead of two
             const int fgrid = bf_fwd_block_h3t_grid(B, H, W);
-            const int64_t pp = ((int64_t)fgrid * 32 + 63) / 64 * 64;
-            const bool fold = h->train_fold_finalize != 0;
+            const int64_t pp = align_up((int64_t)fgrid * 32, 64);
+            const bool fold = h->train_fold_finalize != 0 && 2 * pp <= L.partial_floats;
             float* part_i = fold ? t.partial + (i & 1) * pp : t.partial;
             FwdBlockH3Args fa;
             memset(&fa, 0, sizeof(fa));

@@ -30,6 +30,7 @@
 #include "h3_core.h"
 
 #include "h3v_core.h"
+#include "h3_bands.h"
 
 struct H3VGeom {
     static constexpr int WMAX = 256;                   // columns a workgroup covers (whole image rows)
@@ -51,36 +52,10 @@ struct H3VGeom {
     static_assert(NRI == PD + 2, "input ring");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
     static_assert(2 * IN_PLANE + 1024 < 65536 && 2 * MID_PLANE + NRM * PITCH + 1024 < 65536, "fragment offsets fit the 16-bit ds offset");
+    static constexpr int LEAD_STEPS = 10;              // what a band costs beyond its rows, in steps (bf_band_plan)
 };
 
-struct H3VTile {
-    int y0, nrows;
-    size_t img;
-    int ybase, ystep;            // image row of band-relative row k: ybase + ystep * k (a reversed band walks bottom-up)
-    __device__ __forceinline__ int y(const int k) const { return ybase + ystep * k; }
-};
-
-// A launch walks its bands top-down or (reverse_tiles) bottom-up and last band first: consecutive blocks alternate, so a
-// block starts on the rows the previous one wrote last -- the ones still in the 256 MB Infinity Cache.  Walking up only
-// mirrors the vertical taps (the weight images are loaded with dy -> 2 - dy) and the row addresses.
-__device__ __forceinline__ H3VTile h3v_tile(const FusedH3Args& a, const int t)
-{
-    H3VTile r;
-    const int tt = a.reverse_tiles ? a.ntiles - 1 - t : t;
-    const int b = tt / a.tiles_y, ty = tt - b * a.tiles_y;
-    r.y0 = ty * a.rows_per_tile;
-    r.nrows = min(a.rows_per_tile, a.H - r.y0);
-    r.img = (size_t)b * a.H * a.W * 64;
-    r.ybase = a.reverse_tiles ? r.y0 + r.nrows - 1 : r.y0;
-    r.ystep = a.reverse_tiles ? -1 : 1;
-    return r;
-}
-
-// weight image i = dy * 4 + kind (12 = s2 * identity) as the code's tap row dy: mirrored for a band that walks bottom-up
-__device__ __forceinline__ int h3v_wimage(const FusedH3Args& a, const int i)
-{
-    return (a.reverse_tiles && i < 12) ? (2 - i / 4) * 4 + i % 4 : i;
-}
+using H3VTile = BandUnit;       // a band of whole rows (h3_bands.h)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // role A: conv1.  State that lives across steps: acc[g][3] (mid rows s, s-1, s-2 modulo 3).
@@ -440,7 +415,7 @@ __global__ __launch_bounds__(H3VGeom::NT, 3) void fused_block_h3v_kernel(FusedH3
         __builtin_amdgcn_s_setprio(1);
         H3VRoleA<FULLW> A{a, tin, tmid};
 #pragma unroll
-        for (int i = 0; i < 13; ++i) A.w[i] = reinterpret_cast<const h8*>(a.w1r)[h3v_wimage(a, i) * 64 + lane];
+        for (int i = 0; i < 13; ++i) A.w[i] = reinterpret_cast<const h8*>(a.w1r)[bf_band_wimage(a, i) * 64 + lane];
         A.inv_s = a.aux[0];
         A.relu_floor = a.act1_relu ? 0.f : -__builtin_inff();
         // taps dx = 0,1 of image column c are ring columns c, c+1 (ring column = image column + 1, centre tap dx = 1)
@@ -456,7 +431,7 @@ __global__ __launch_bounds__(H3VGeom::NT, 3) void fused_block_h3v_kernel(FusedH3
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));               // weight / scale loads
 
         for (int ti = blockIdx.x; ti < a.ntiles; ti += gridDim.x) {
-            const H3VTile t = h3v_tile(a, ti);
+            const H3VTile t = bf_band_unit<false>(a, ti);
             h3v_barrier();                                       // prologue: input row 0 has landed
             const int nsteps = t.nrows + 6;
             int islot = 0;                                       // s mod NRI
@@ -479,7 +454,7 @@ __global__ __launch_bounds__(H3VGeom::NT, 3) void fused_block_h3v_kernel(FusedH3
         __builtin_amdgcn_s_setprio(H3V_PRIO_B);
         H3VRoleB Bv{a, tin, tmid, tout};
 #pragma unroll
-        for (int i = 0; i < 13; ++i) Bv.w[i] = reinterpret_cast<const h8*>(a.w2r)[h3v_wimage(a, i) * 64 + lane];
+        for (int i = 0; i < 13; ++i) Bv.w[i] = reinterpret_cast<const h8*>(a.w2r)[bf_band_wimage(a, i) * 64 + lane];
         Bv.inv_s2 = a.aux[48];
         Bv.shs = *reinterpret_cast<const f32x4*>(a.aux + 32 + q * 4) * (1.0f / Bv.inv_s2);     // inv_s2 is a power of two: exact
         Bv.rp = (q & 1) * Gm::MID_PLANE + (c0 + (q >> 1)) * 16;
@@ -493,7 +468,7 @@ __global__ __launch_bounds__(H3VGeom::NT, 3) void fused_block_h3v_kernel(FusedH3
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));
 
         for (int ti = blockIdx.x; ti < a.ntiles; ti += gridDim.x) {
-            const H3VTile t = h3v_tile(a, ti);
+            const H3VTile t = bf_band_unit<false>(a, ti);
             h3v_barrier();                                       // prologue barrier
             const int nsteps = t.nrows + 6;
             int xslot = Gm::NRI - 1;                             // (s - 1) mod NRI
@@ -526,7 +501,7 @@ __global__ __launch_bounds__(H3VGeom::NT, 3) void fused_block_h3v_kernel(FusedH3
         constexpr int INFLIGHT = 2 * 2 * Gm::PIECES;           // pieces of the two rows younger than the one awaited
         const bool lo_regs = a.compact && Cv.plane0 == 2;      // compact layout: this wave's planes are the fp8 lo planes
         for (int ti = blockIdx.x; ti < a.ntiles; ti += gridDim.x) {
-            const H3VTile t = h3v_tile(a, ti);
+            const H3VTile t = bf_band_unit<false>(a, ti);
             if (loader && lo_regs) {
                 // prologue: rows 0 and 1 decoded into their slots, row 2 requested
                 Cv.lo_request(t, 0); Cv.lo_commit(0);
@@ -586,25 +561,6 @@ __global__ __launch_bounds__(H3VGeom::NT, 3) void fused_block_h3v_kernel(FusedH3
 #endif
 }
 
-// bands: every image is cut into ceil(H / rows) bands of `rows` rows; one band = one unit of work of a workgroup.
-// rows is chosen so that the slowest CU (ceil(bands / CUs) bands of rows + 10 steps each) finishes earliest.
-static int h3v_rows_per_tile(const int B, const int H, const int cus)
-{
-    int best = H;
-    long best_cost = -1;
-    for (int ty = 1; ty <= (H + 7) / 8; ++ty) {
-        const int rows = (H + ty - 1) / ty;
-        if ((H + rows - 1) / rows != ty) continue;
-        const long tiles = (long)B * ty;
-        const long cost = ((tiles + cus - 1) / cus) * (rows + 10);
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = rows;
-        }
-    }
-    return best;
-}
-
 bool bf_fused_block_h3v_supports(int H, int W) { return W >= 1 && W <= H3VGeom::WMAX && H >= 1; }
 
 hipError_t bf_launch_fused_block_h3v(const FusedH3Args& args, hipStream_t s)
@@ -613,16 +569,15 @@ hipError_t bf_launch_fused_block_h3v(const FusedH3Args& args, hipStream_t s)
     FusedH3Args a = args;
     if (!a.zeros || !a.dump || !bf_fused_block_h3v_supports(a.H, a.W)) return hipErrorInvalidValue;
     if ((int64_t)a.H * a.W * 64 >= ((int64_t)1 << 32)) return hipErrorInvalidValue;      // 32-bit in-image offsets
-    const int cus = 256;
-    a.rows_per_tile = h3v_rows_per_tile(a.B, a.H, cus);
+    const BandPlan p = bf_band_plan(a.B, a.H, 1, Gm::LEAD_STEPS);
+    a.rows_per_tile = p.rows_per_tile;
     a.tiles_x = 1;
-    a.tiles_y = (a.H + a.rows_per_tile - 1) / a.rows_per_tile;
-    a.ntiles = a.B * a.tiles_y;
-    const int grid = a.ntiles < cus ? a.ntiles : cus;
+    a.tiles_y = p.tiles_y;
+    a.ntiles = p.ntiles;
     const bool fullw = a.W == Gm::WMAX;
     void (*kernel)(FusedH3Args) = fullw ? fused_block_h3v_kernel<true> : fused_block_h3v_kernel<false>;
     const hipError_t e = bf_set_max_lds(reinterpret_cast<const void*>(kernel), Gm::LDS_BYTES);      // once per device
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(Gm::NT), Gm::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(Gm::NT), Gm::LDS_BYTES, s, a);
     return hipGetLastError();
 }

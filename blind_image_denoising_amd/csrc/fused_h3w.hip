@@ -31,6 +31,7 @@
 //   * rows and columns outside the image are forced to zero in every ring (they are the NEXT convolution's zero padding,
 //     not values computed from padded input).
 #include "h3v_core.h"
+#include "h3_bands.h"
 
 // wave priorities (s_setprio) per role; H3W_PRIO_SET picks a preset for A/B builds: 1 = younger roles higher (0,1,2,3),
 // 2 = older roles higher (3,2,1,0), 3 = second convolutions high (0,2,0,2), 4 = first convolutions high (2,0,2,0)
@@ -93,42 +94,21 @@ struct H3WGeom {
     static_assert(3 * X0_PLANE + NRX0 * PITCH < 65536, "fragment offsets fit the 16-bit ds offset");
 };
 
-struct H3WTile {
-    int nrows, b;                // rows of the band, image index
-    size_t img;
-    int ybase, ystep;            // image row of band-relative row k: ybase + ystep * k (a reversed band walks bottom-up)
+struct H3WTile : BandUnit {      // a band of one strip (h3_bands.h) + the strip's columns
     int X0, X1;                  // output columns [X0, X1)
     int G0;                      // image column of grid column 0
     int D0, D1;                  // x0 columns fetched: [D0, D1), inside the grid and the image
-    __device__ __forceinline__ int y(const int k) const { return ybase + ystep * k; }
 };
 
-// unit t of a launch = (image, band of rows, strip); reverse_tiles: last unit first and bottom-up (consecutive launches
-// alternate, so a launch starts on what the previous one wrote last -- still in the 256 MB Infinity Cache; walking up only
-// mirrors the vertical taps: the weight images are loaded with dy -> 2 - dy)
 __device__ __forceinline__ H3WTile h3w_tile(const FusedH3WArgs& a, const int t)
 {
-    H3WTile r;
-    const int tt = a.reverse_tiles ? a.ntiles - 1 - t : t;
-    const int sx = tt % a.nstrips, rest = tt / a.nstrips;
-    const int b = rest / a.tiles_y, ty = rest - b * a.tiles_y;
-    const int y0 = ty * a.rows_per_tile;
-    r.nrows = min(a.rows_per_tile, a.H - y0);
-    r.b = b;
-    r.img = (size_t)b * a.H * a.W * 64;
-    r.ybase = a.reverse_tiles ? y0 + r.nrows - 1 : y0;
-    r.ystep = a.reverse_tiles ? -1 : 1;
-    r.X0 = sx * H3WGeom::SW;
+    H3WTile r{bf_band_unit<false>(a, t)};
+    r.X0 = r.sx * H3WGeom::SW;
     r.X1 = min(a.W, r.X0 + H3WGeom::SW);
     r.G0 = min(max(r.X0 - 8, 0), max(a.W - H3WGeom::GW, 0));
     r.D0 = max(0, (r.X0 - 4) & ~7);
     r.D1 = min(a.W, (r.X1 + 4 + 7) & ~7);
     return r;
-}
-
-__device__ __forceinline__ int h3w_wimage(const FusedH3WArgs& a, const int i)
-{
-    return (a.reverse_tiles && i < 12) ? (2 - i / 4) * 4 + i % 4 : i;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -152,7 +132,7 @@ struct H3WRoleA {
     {
         const int q = lane >> 4;
 #pragma unroll
-        for (int i = 0; i < 13; ++i) w[i] = reinterpret_cast<const h8*>(wimg)[h3w_wimage(a, i) * 64 + lane];
+        for (int i = 0; i < 13; ++i) w[i] = reinterpret_cast<const h8*>(wimg)[bf_band_wimage(a, i) * 64 + lane];
         inv_s = aux[0];
         relu_floor = a.act1_relu ? 0.f : -__builtin_inff();
         // taps dx = 0, 1 of grid column c are ring columns c, c + 1 (ring column = grid column + 1, centre tap dx = 1)
@@ -265,7 +245,7 @@ struct H3WRoleB {
     {
         const int q = lane >> 4;
 #pragma unroll
-        for (int i = 0; i < 13; ++i) w[i] = reinterpret_cast<const h8*>(wimg)[h3w_wimage(a, i) * 64 + lane];
+        for (int i = 0; i < 13; ++i) w[i] = reinterpret_cast<const h8*>(wimg)[bf_band_wimage(a, i) * 64 + lane];
         inv_s2 = aux[48];
         shs = *reinterpret_cast<const f32x4*>(aux + 32 + q * 4) * (1.0f / inv_s2);     // inv_s2 is a power of two: exact
         rp = (q & 1) * Gm::M_PLANE + (gc0 + (q >> 1)) * 16;
@@ -712,27 +692,6 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
 #endif
 }
 
-static int h3w_nstrips(const int W) { return (W + H3WGeom::SW - 1) / H3WGeom::SW; }
-
-// bands: every strip of every image is cut into ceil(H / rows) bands of `rows` rows; one band of one strip = one unit of work
-// of a workgroup.  rows is chosen so that the slowest CU (ceil(units / CUs) units of rows + 14 steps each) finishes earliest.
-static int h3w_rows_per_tile(const int B, const int H, const int nstrips, const int cus)
-{
-    int best = H;
-    long best_cost = -1;
-    for (int ty = 1; ty <= (H + 7) / 8; ++ty) {
-        const int rows = (H + ty - 1) / ty;
-        if ((H + rows - 1) / rows != ty) continue;
-        const long tiles = (long)B * ty * nstrips;
-        const long cost = ((tiles + cus - 1) / cus) * (rows + H3WGeom::LEAD + 2);
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = rows;
-        }
-    }
-    return best;
-}
-
 bool bf_fused_block2_h3w_supports(int H, int W) { return W >= 1 && H >= 1; }
 
 hipError_t bf_launch_fused_block2_h3w(const FusedH3WArgs& args, hipStream_t s)
@@ -741,16 +700,15 @@ hipError_t bf_launch_fused_block2_h3w(const FusedH3WArgs& args, hipStream_t s)
     FusedH3WArgs a = args;
     if (!a.zeros || !a.in || (!a.out && !a.head_wh) || !bf_fused_block2_h3w_supports(a.H, a.W)) return hipErrorInvalidValue;
     if ((int64_t)a.H * a.W * 64 >= ((int64_t)1 << 32)) return hipErrorInvalidValue;      // 32-bit in-image offsets
-    const int cus = 256;
-    a.nstrips = h3w_nstrips(a.W);
-    a.rows_per_tile = h3w_rows_per_tile(a.B, a.H, a.nstrips, cus);
-    a.tiles_y = (a.H + a.rows_per_tile - 1) / a.rows_per_tile;
-    a.ntiles = a.B * a.tiles_y * a.nstrips;
-    const int grid = a.ntiles < cus ? a.ntiles : cus;
+    const BandPlan p = bf_band_plan(a.B, a.H, (a.W + Gm::SW - 1) / Gm::SW, Gm::LEAD + 2);
+    a.nstrips = p.nstrips;
+    a.rows_per_tile = p.rows_per_tile;
+    a.tiles_y = p.tiles_y;
+    a.ntiles = p.ntiles;
     if (a.head_wh && (!a.head_out || a.Ho < 1 || a.Wo < 1 || a.Ho > a.H || a.Wo > a.W)) return hipErrorInvalidValue;
     void (*kernel)(FusedH3WArgs) = a.head_wh ? fused_block2_h3w_kernel<true> : fused_block2_h3w_kernel<false>;
     const hipError_t e = bf_set_max_lds(reinterpret_cast<const void*>(kernel), Gm::LDS_BYTES);      // once per device
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(Gm::NT), Gm::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(Gm::NT), Gm::LDS_BYTES, s, a);
     return hipGetLastError();
 }

@@ -36,6 +36,7 @@
 #include "bf_common.h"
 #include "h3_core.h"
 #include "h3v_core.h"
+#include "h3_bands.h"
 
 typedef __fp16 hu_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
@@ -96,40 +97,24 @@ struct H3UGeom {
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-struct H3UTile {
-    int nrows;
-    size_t img;                  // byte offset of the image in an fp32 NHWC tensor of 16 channels
-    int ybase, ystep;            // image row of band-relative row k: ybase + ystep * k (a reversed band walks bottom-up)
+struct H3UTile : BandUnit {      // a band of one strip of an fp32 NHWC tensor of 16 channels (h3_bands.h) + the strip's columns
     int X0, X1;                  // own (output) columns [X0, X1)
     int G0, go;                  // image column of grid column 0; grid column of X0
-    __device__ __forceinline__ int y(const int k) const { return ybase + ystep * k; }
 };
 
 #ifndef H3U_XCD_ORDER
-#define H3U_XCD_ORDER 1
+#define H3U_XCD_ORDER 1              // XCD-contiguous unit order (h3_bands.h); 0 = launch order, for A/B builds
 #endif
 __device__ __forceinline__ H3UTile h3u_tile(const BwdBlockH3Args& a, const int t)
 {
-    H3UTile r;
-    // XCD-contiguous tile order (train_fwd_h3t.hip): the 16 halo columns two neighbouring strips share and the LEAD halo rows of vertically
-    // adjacent bands come out of one XCD's L2 (H3U_XCD_ORDER 0: 934 MB per launch for 671 MB algorithmic)
-    const int tp = (H3U_XCD_ORDER && (a.ntiles & 7) == 0) ? (t & 7) * (a.ntiles >> 3) + (t >> 3) : t;
-    const int tt = a.reverse ? a.ntiles - 1 - tp : tp;
-    const int sx = tt % a.nstrips, rest = tt / a.nstrips;
-    const int b = rest / a.tiles_y, ty = rest - b * a.tiles_y;
-    const int y0 = ty * a.rows_per_tile;
-    r.nrows = min(a.rows_per_tile, a.H - y0);
-    r.img = (size_t)b * a.H * a.W * 64;
-    r.ybase = a.reverse ? y0 + r.nrows - 1 : y0;
-    r.ystep = a.reverse ? -1 : 1;
-    r.X0 = sx * H3UGeom::SW;
+    H3UTile r{bf_band_unit<H3U_XCD_ORDER != 0>(a, t)};
+    r.X0 = r.sx * H3UGeom::SW;
     r.X1 = min(a.W, r.X0 + H3UGeom::SW);
     r.G0 = max(r.X0 - 8, 0);
     r.go = r.X0 - r.G0;
     return r;
 }
 
-__device__ __forceinline__ int h3u_wimage(const BwdBlockH3Args& a, const int i) { return a.reverse ? (2 - i / 4) * 4 + i % 4 : i; }
 __device__ __forceinline__ int h3u_mod(const int v, const int n) { return ((v % n) + n) % n; }
 
 // the 15 MFMAs of one 16-pixel group and step (see train_fwd_h3t.hip)
@@ -271,7 +256,7 @@ struct H3UConv {
     {
         const int q = lane >> 4;
 #pragma unroll
-        for (int i = 0; i < 12; ++i) w[i] = reinterpret_cast<const h8*>(pack)[h3u_wimage(a, i) * 64 + lane];
+        for (int i = 0; i < 12; ++i) w[i] = reinterpret_cast<const h8*>(pack)[bf_band_wimage(a, i) * 64 + lane];
         w[12] = w[0];
         inv_s = pack[BF_H3R_WPACK_FLOATS];
         relu = a.act_relu != 0;
@@ -907,36 +892,17 @@ __global__ __launch_bounds__(H3UGeom::NT, 3) void bwd_block_h3t_kernel(BwdBlockH
     else h3u_role_w<2>(a, lane);
 }
 
-static int h3u_nstrips(const int W) { return (W + H3UGeom::SW - 1) / H3UGeom::SW; }
-
-// bands: every strip of every image is cut into ceil(H / rows) bands; one band of one strip = one unit of work of a workgroup
-static int h3u_rows_per_tile(const int B, const int H, const int nstrips, const int cus)
-{
-    int best = H;
-    long best_cost = -1;
-    for (int ty = 1; ty <= (H + 7) / 8; ++ty) {
-        const int rows = (H + ty - 1) / ty;
-        if ((H + rows - 1) / rows != ty) continue;
-        const long tiles = (long)B * ty * nstrips;
-        const long cost = ((tiles + cus - 1) / cus) * (rows + H3UGeom::LEAD + 2);
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = rows;
-        }
-    }
-    return best;
-}
-
 bool bf_bwd_block_h3t_supports(int H, int W) { return W >= 1 && H >= 1; }
 
-// workgroups (= rows of wpartial0 / wpartial1 / stats) a launch uses
-int bf_bwd_block_h3t_grid(int B, int H, int W)
+static BandPlan h3u_plan(const int B, const int H, const int W)
 {
-    const int ns = h3u_nstrips(W);
-    const int rows = h3u_rows_per_tile(B, H, ns, 256);
-    const long tiles = (long)B * ((H + rows - 1) / rows) * ns;
-    return (int)(tiles < 256 ? tiles : 256);
+    return bf_band_plan(B, H, (W + H3UGeom::SW - 1) / H3UGeom::SW, H3UGeom::LEAD + 2);
 }
+
+// workgroups (= rows of wpartial0 / wpartial1 / stats) a launch uses
+int bf_bwd_block_h3t_grid(int B, int H, int W) { return h3u_plan(B, H, W).grid; }
+// rows of all strips of all images: the work of a launch in steps, whatever the bands
+int64_t bf_bwd_block_h3t_strip_rows(int B, int H, int W) { return (int64_t)B * H * h3u_plan(B, H, W).nstrips; }
 
 hipError_t bf_launch_bwd_block_h3t(const BwdBlockH3Args& args, hipStream_t s)
 {
@@ -948,15 +914,14 @@ hipError_t bf_launch_bwd_block_h3t(const BwdBlockH3Args& args, hipStream_t s)
     if (a.fin_partial && (a.fin_partial == a.stats || a.fin_nblk <= 0 || !(a.fin_count > 0.0) || !a.fin_gamma || !a.fin_meaninv || !a.fin_dgamma))
         return hipErrorInvalidValue;
     if (a.out == a.a || a.out == a.g || a.out == a.c || (a.bnc && (!a.stats || a.out == a.bnc))) return hipErrorInvalidValue;
-    const int cus = 256;
-    a.nstrips = h3u_nstrips(a.W);
-    a.rows_per_tile = h3u_rows_per_tile(a.B, a.H, a.nstrips, cus);
-    a.tiles_y = (a.H + a.rows_per_tile - 1) / a.rows_per_tile;
-    a.ntiles = a.B * a.tiles_y * a.nstrips;
-    const int grid = a.ntiles < cus ? a.ntiles : cus;
+    const BandPlan p = h3u_plan(a.B, a.H, a.W);
+    a.nstrips = p.nstrips;
+    a.rows_per_tile = p.rows_per_tile;
+    a.tiles_y = p.tiles_y;
+    a.ntiles = p.ntiles;
     void (*kernel)(BwdBlockH3Args) = a.bnc ? bwd_block_h3t_kernel<true> : bwd_block_h3t_kernel<false>;
     const hipError_t e = bf_set_max_lds(reinterpret_cast<const void*>(kernel), Gm::LDS_BYTES);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(Gm::NT), Gm::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(Gm::NT), Gm::LDS_BYTES, s, a);
     return hipGetLastError();
 }

@@ -25,6 +25,7 @@
 #include "bf_common.h"
 #include "h3_core.h"
 #include "h3v_core.h"
+#include "h3_bands.h"
 
 struct H3TGeom {
     static constexpr int WMAX = 256;                   // columns a workgroup covers (whole image rows)
@@ -46,6 +47,7 @@ struct H3TGeom {
     static_assert(UNROLL % NRM == 0 && UNROLL % NRO == 0 && UNROLL % NRI == 0 && UNROLL % 3 == 0 && UNROLL % 2 == 0, "static slots");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
     static_assert(3 * IN_PLANE + NRI * PITCH < 65536 && 3 * MID_PLANE + NRM * PITCH < 65536, "fragment offsets fit the 16-bit ds offset");
+    static constexpr int LEAD_STEPS = 10;              // what a band costs beyond its rows, in steps (bf_band_plan)
 };
 
 struct H3TTile {
@@ -58,12 +60,11 @@ struct H3TTile {
 #ifndef H3T_XCD_ORDER
 #define H3T_XCD_ORDER 1
 #endif
+// This kernel keeps its own copy of bf_band_unit / bf_band_wimage (h3_bands.h): through the shared decode its full-width
+// instantiations came out one scalar move longer, every loop behind it 4 bytes further on, and a training step 0.3 % slower.
 __device__ __forceinline__ H3TTile h3t_tile(const FwdBlockH3Args& a, const int t)
 {
     H3TTile r;
-    // workgroup ids go round the 8 XCDs: tile t of the launch order becomes tile (t mod 8) * ntiles / 8 + t / 8, so that an XCD walks a
-    // contiguous eighth of the bands and the halo rows two vertically adjacent bands both read are found in ITS L2 (H3T_XCD_ORDER 0:
-    // neighbours on different XCDs, every halo row fetched twice from the Infinity Cache / HBM: 626 MB per launch for 537 MB algorithmic)
     const int tp = (H3T_XCD_ORDER && (a.ntiles & 7) == 0) ? (t & 7) * (a.ntiles >> 3) + (t >> 3) : t;
     const int tt = a.reverse ? a.ntiles - 1 - tp : tp;
     const int b = tt / a.tiles_y, ty = tt - b * a.tiles_y;
@@ -75,7 +76,6 @@ __device__ __forceinline__ H3TTile h3t_tile(const FwdBlockH3Args& a, const int t
     return r;
 }
 
-// weight image i = dy * 4 + kind as the code's tap row dy: mirrored for a band that walks bottom-up
 __device__ __forceinline__ int h3t_wimage(const FwdBlockH3Args& a, const int i) { return a.reverse ? (2 - i / 4) * 4 + i % 4 : i; }
 
 // the 15 MFMAs of one 16-pixel group and step: vertical taps 2 / 1 / 0 of the ring row in `cur` go to the accumulators of the
@@ -599,31 +599,13 @@ __global__ __launch_bounds__(H3TGeom::NT, 3) void fwd_block_h3t_kernel(FwdBlockH
 
 bool bf_fwd_block_h3t_supports(int H, int W) { return W >= 1 && W <= H3TGeom::WMAX && H >= 1; }
 
-// bands: as the inference kernel (fused_h3v.hip): rows per band such that the slowest CU finishes earliest
-static int h3t_rows_per_tile(const int B, const int H, const int cus)
-{
-    int best = H;
-    long best_cost = -1;
-    for (int ty = 1; ty <= (H + 7) / 8; ++ty) {
-        const int rows = (H + ty - 1) / ty;
-        if ((H + rows - 1) / rows != ty) continue;
-        const long tiles = (long)B * ty;
-        const long cost = ((tiles + cus - 1) / cus) * (rows + 10);
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = rows;
-        }
-    }
-    return best;
-}
+static BandPlan h3t_plan(const int B, const int H) { return bf_band_plan(B, H, 1, H3TGeom::LEAD_STEPS); }
 
 // workgroups (= rows of a.stats) a launch uses
 int bf_fwd_block_h3t_grid(int B, int H, int W)
 {
     (void)W;
-    const int rows = h3t_rows_per_tile(B, H, 256);
-    const long tiles = (long)B * ((H + rows - 1) / rows);
-    return (int)(tiles < 256 ? tiles : 256);
+    return h3t_plan(B, H).grid;
 }
 
 hipError_t bf_launch_fwd_block_h3t(const FwdBlockH3Args& args, hipStream_t s)
@@ -635,11 +617,10 @@ hipError_t bf_launch_fwd_block_h3t(const FwdBlockH3Args& args, hipStream_t s)
     if (a.fin_partial && (!a.pre_c || a.fin_partial == a.stats || a.fin_nblk <= 0 || !(a.fin_count > 0.0) || !a.fin_mm || !a.fin_mv || !a.fin_scale || !a.fin_meaninv))
         return hipErrorInvalidValue;
     if (a.c_out == a.x || a.c_out == a.pre_c || a.t_out == a.x || (a.t_out && a.t_out == a.pre_c)) return hipErrorInvalidValue;
-    const int cus = 256;
-    a.rows_per_tile = h3t_rows_per_tile(a.B, a.H, cus);
-    a.tiles_y = (a.H + a.rows_per_tile - 1) / a.rows_per_tile;
-    a.ntiles = a.B * a.tiles_y;
-    const int grid = a.ntiles < cus ? a.ntiles : cus;
+    const BandPlan p = h3t_plan(a.B, a.H);
+    a.rows_per_tile = p.rows_per_tile;
+    a.tiles_y = p.tiles_y;
+    a.ntiles = p.ntiles;
     const bool fullw = a.W == Gm::WMAX, pre = a.pre_c != nullptr, wt = a.t_out != nullptr;
     void (*kernel)(FwdBlockH3Args) = nullptr;
 #define BF_PICK(F, P, T) if (fullw == F && pre == P && wt == T) kernel = fwd_block_h3t_kernel<F, P, T>;
@@ -648,6 +629,6 @@ hipError_t bf_launch_fwd_block_h3t(const FwdBlockH3Args& args, hipStream_t s)
 #undef BF_PICK
     const hipError_t e = bf_set_max_lds(reinterpret_cast<const void*>(kernel), Gm::LDS_BYTES);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(Gm::NT), Gm::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(Gm::NT), Gm::LDS_BYTES, s, a);
     return hipGetLastError();
 }

@@ -424,7 +424,8 @@ def test_conv3x3_h3_affine_add_on_load(shape, relu):
 
 # the whole training forward of a block in one row-streaming kernel (train_fwd_h3t.hip): full 256-column rows and narrower ones,
 # bands shorter than the pipeline (1 and 2 rows), more bands than workgroups (300 x 8 rows), both walking directions
-FWD_BLOCK_SHAPES = [(1, 1, 1), (2, 2, 5), (1, 5, 256), (3, 33, 47), (2, 64, 256), (1, 130, 255), (2, 40, 70), (300, 8, 16)]
+# (2, 64, 256) and (2, 64, 255): 16 bands, a multiple of 8 -> the XCD-contiguous band order, walked top-down and (H + W odd) bottom-up
+FWD_BLOCK_SHAPES = [(1, 1, 1), (2, 2, 5), (1, 5, 256), (3, 33, 47), (2, 64, 256), (2, 64, 255), (1, 130, 255), (2, 40, 70), (300, 8, 16)]
 
 
 @pytest.mark.parametrize("shape", FWD_BLOCK_SHAPES)
@@ -489,7 +490,10 @@ def _block_backward_oracle(a, g, c, coef, w0, w1, relu):
 
 # one to three strips of 128 columns, grids clamped to the left edge, partial last strips, bands shorter than the pipeline,
 # more units than workgroups (70 x 40 x 256 = 280 strips x bands), both walking directions
-BWD_BLOCK_SHAPES = [(1, 1, 1), (2, 3, 7), (1, 12, 128), (3, 33, 47), (2, 40, 200), (1, 70, 256), (2, 24, 300), (70, 40, 256)]
+# (2, 32, 136) and (1, 64, 129): 2 strips x 8 bands = 16 units, a multiple of 8 -> the XCD-contiguous unit order, walked top-down and
+# (H + W odd) bottom-up
+BWD_BLOCK_SHAPES = [(1, 1, 1), (2, 3, 7), (1, 12, 128), (3, 33, 47), (2, 40, 200), (1, 70, 256), (2, 24, 300), (70, 40, 256), (2, 32, 136),
+                    (1, 64, 129)]
 
 
 @pytest.mark.parametrize("shape", BWD_BLOCK_SHAPES)

@@ -157,6 +157,56 @@ def test_workspace_and_packed_queries():
     assert L.bf_packed_bytes(m._h) % 256 == 0
 
 
+def _band_plan_grid(B, H, nstrips, lead_steps, cap=256):
+    """restatement of bf_band_plan (csrc/h3_bands.h): rows per band such that the slowest of `cap` workgroups finishes earliest
+    (first minimum over ty = 1 .. ceil(H / 8), a ty its own rows do not reproduce is skipped); returns the launch grid"""
+    best, best_cost = H, None
+    for ty in range(1, (H + 7) // 8 + 1):
+        rows = -(-H // ty)
+        if -(-H // rows) != ty:
+            continue
+        cost = -(-B * ty * nstrips // cap) * (rows + lead_steps)
+        if best_cost is None or cost < best_cost:
+            best, best_cost = rows, cost
+    return min(B * -(-H // best) * nstrips, cap)
+
+
+def test_band_plan_sizes_the_block_kernel_scratch():
+    """launch grid and workspace sizing of the streaming block kernels come from one planner: the scratch queries of the training
+    block kernels (rows of partial sums = workgroups of the launch) against the Python restatement"""
+    from test_gpu_kernels import BWD_BLOCK_SHAPES, FWD_BLOCK_SHAPES
+    L = N.lib()
+    rng = np.random.default_rng(20)
+    shapes = sorted(set(FWD_BLOCK_SHAPES) | set(BWD_BLOCK_SHAPES)) + [(32, 256, 256), (8, 512, 512)]
+    shapes += [(int(rng.integers(1, 81)), int(rng.integers(1, 601)), int(rng.integers(1, 701))) for _ in range(300)]
+    P = 13 * 64 * 4 + 64
+    fixed = 4 * P + 2 * 2304 + 16
+    for B, H, W in shapes:
+        fwd = _band_plan_grid(B, H, 1, 10)
+        bwd = _band_plan_grid(B, H, -(-W // 128), 10)
+        assert L.bf_debug_fwd_block_h3t_scratch_floats(B, H, W) == fixed + fwd * 32, (B, H, W)
+        assert L.bf_debug_bwd_block_h3t_scratch_floats(B, H, W) == fixed + bwd * (2 * 2304 + 32), (B, H, W)
+
+
+# (B, H, W) -> (training, inference) workspace bytes of the canonical 1x18 model, recorded from the build in front of the shared
+# band planner: the planner and the folded forward's second statistics buffer must not move a byte
+WORKSPACE_BYTES_1X18 = {
+    (32, 256, 256): (8128070400, 402655232),
+    (8, 512, 512): (8128070400, 402655232),
+    (3, 40, 50): (30264832, 2361344),
+    (70, 40, 256): (2893775872, 220203008),
+    (1, 1, 1): (1876432, 2240),
+}
+
+
+def test_workspace_bytes_are_pinned():
+    m = bf.model_builder(O.canonical_config(no_layers=18)["model"], device="cpu").hydra
+    L = N.lib()
+    for (B, H, W), (train, infer) in WORKSPACE_BYTES_1X18.items():
+        assert L.bf_workspace_bytes(m._h, N.BF_MODE_TRAIN, B, H, W) == train, (B, H, W)
+        assert L.bf_workspace_bytes(m._h, N.BF_MODE_INFERENCE, B, H, W) == infer, (B, H, W)
+
+
 def test_load_model_errors_mirror_reference():
     with pytest.raises(ValueError, match="cannot be empty"):
         bf.load_model("")
