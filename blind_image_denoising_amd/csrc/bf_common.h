@@ -150,7 +150,7 @@ struct FusedH3Args {
     int B, H, W;
     int tiles_x, tiles_y, ntiles;   // filled in by the launcher
     int rows_per_tile;    // full-row streaming kernel (fused_h3v.hip): rows per band, filled in by the launcher
-    int reverse_tiles;    // full-row streaming kernel: walk the bands last to first (see forward_common)
+    int reverse_tiles;    // full-row streaming kernel: walk the bands last to first (see make_forward_plan, engine_infer.hip)
     int variant;          // kernel selection: < 0 = library default (bf_set_h3_variant), else as bf_set_option("h3_variant")
     int act1_relu;
     const void* zeros;    // >= 64 B of zeros, 16-B aligned (source of out-of-image elements)
@@ -165,12 +165,27 @@ struct FusedH3Args {
     int* status;           // |= BF_STATUS_F16_RANGE when a block output is not finite
     int compact = 0;       // full-row streaming kernel only: in / out are compact split-planar (fp8 lo planes, see bf_h3c_encode8)
 };
+// What decides the kernel of ONE split-f16 block, and the choice (fused_h3.hip holds the one rule).  A forward asks once per step
+// with what the launch will really carry (bf_select_fused_block_h3) and launches that (bf_launch_fused_block_h3_as);
+// bf_launch_fused_block_h3 = both, for callers without a plan.
+struct H3Request {
+    int B, H, W;
+    int variant;          // FusedH3Args::variant
+    bool head;            // the launch carries the head epilogue (FusedH3Args::head_wh)
+    bool compact;         // FusedH3Args::compact
+};
+enum class H3Kernel { Tiles32, Tiles16, FullRow };     // row-streaming tile kernel on 16 x 32 / 16 x 16 tiles, full-row streaming kernel
+struct H3Choice {
+    H3Kernel kernel;
+    bool bottom_up;       // the request carried bit 8: the launch walks last to first whatever the band order says (tests)
+};
+H3Choice   bf_select_fused_block_h3(const H3Request& r);
+hipError_t bf_launch_fused_block_h3_as(const FusedH3Args& a, H3Kernel k, hipStream_t s);
 hipError_t bf_launch_fused_block_h3(const FusedH3Args& a, hipStream_t s);
-// true when bf_launch_fused_block_h3 would run the full-row streaming kernel for these arguments (the one kernel that reads and
-// writes the compact layout)
-bool       bf_fused_block_h3_is_streaming(const FusedH3Args& a);
-bool       bf_fused_block_h3_use_pairs(const FusedH3Args& a);   // two blocks per launch: default selection with >= 4 096 strip rows of >= 24-row images, or a forced streaming variant
-const char* bf_fused_block_h3_kernel_name(const FusedH3Args& a);
+// two blocks per launch preferred for a forward of such blocks (r.head / r.compact: never): default selection with >= 4 096 strip
+// rows of >= 24-row images, or a forced variant that selects the full-row streaming kernel
+bool       bf_fused_block_h3_use_pairs(const H3Request& r);
+const char* bf_fused_block_h3_kernel_name(H3Kernel k);
 const char* bf_fused_block_kernel_name();                      // conv3x3_c16.hip: the exact-fp32 fused block
 // library default of FusedH3Args::variant (handle-less debug entries): 4 = full-row streaming kernel where it applies
 // (W <= 256), 2 = row-streaming tile kernel on 16 x 16 tiles, every other value (1; 0 and 3 of retired kernels) = on 16 x 32 tiles
@@ -353,7 +368,7 @@ struct HeadTrainArgs {
     int B, H, W, cout, denormalize;
     float v_min, v_max, hinge, cutoff, dscale; // dscale = mae_multiplier*depth_weight/numel
     float dfeat_scale;                         // power of two on the dfeat output only (gradient scaling of the split-f16
-                                               // backward, engine.hip bf_train_step); the head's own gradients (M) are not scaled
+                                               // backward, engine_train.hip bf_train_step); the head's own gradients (M) are not scaled
 };
 hipError_t bf_launch_head_train(const HeadTrainArgs& a, int grid, hipStream_t s);
 // RMSE / SSIM loss terms (loss_terms.hip): additive dL/dpred from the prediction and the head's per-image sums

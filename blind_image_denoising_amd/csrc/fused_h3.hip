@@ -474,28 +474,27 @@ void bf_set_h3_variant(int v) { g_h3_variant = v < 0 ? -1 : v; }
 // Below one 16 x 32 tile per CU (or between one and two) the 16 x 16 tiles of variant 2 -- two 4-wave workgroups per CU -- put more of
 // the chip to work: resnet 1x18 on one 256 x 256 image 149 us for 177, one 128 x 128 image 138 for 166, three 256 x 256 images 241 for
 // 267; from 512 tiles on the larger tile is 3-5 % faster (tools/exp/small_batch_variants.py).
-static int h3_default_variant(const FusedH3Args& a)
+static int h3_default_variant(const H3Request& a)
 {
     // (short AND narrow images -- under 24 rows, up to 128 columns -- stay on tiles: 2 000 x 4 x 64 1 186 us on tiles, 1 559 streaming)
-    if (!a.head_wh && bf_fused_block_h3v_supports(a.H, a.W) && (int64_t)a.B * a.H >= 3072 && (a.H >= 24 || a.W > 128)) return 4;
+    if (!a.head && bf_fused_block_h3v_supports(a.H, a.W) && (int64_t)a.B * a.H >= 3072 && (a.H >= 24 || a.W > 128)) return 4;
     const int64_t tiles32 = (int64_t)a.B * ((a.H + 15) / 16) * ((a.W + 31) / 32);
-    return (!a.head_wh && !a.compact && tiles32 < 512 && tiles32 != 256) ? 2 : 1;
+    return (!a.head && !a.compact && tiles32 < 512 && tiles32 != 256) ? 2 : 1;
 }
 
 // The one selection rule.  The value asked for is the call's own (a.variant), else the process-wide override, else the default
 // for the shape; bit 8 of it (tests: the bottom-up walk of the full-row streaming kernel) is not part of the choice.  4 is the
 // full-row streaming kernel where it applies (images up to 256 columns, no head epilogue), 2 the tile kernel on 16 x 16 tiles, and
 // EVERY other value -- 1, the numbers of retired kernels (0, 3), anything unknown -- the tile kernel on 16 x 32 tiles.
-static int h3_requested(const FusedH3Args& a)
+H3Choice bf_select_fused_block_h3(const H3Request& a)
 {
-    return a.variant >= 0 ? a.variant : (g_h3_variant >= 0 ? g_h3_variant : h3_default_variant(a));
-}
-enum class H3Kernel { Tiles32, Tiles16, FullRow };
-static H3Kernel h3_select(const FusedH3Args& a)
-{
-    const int variant = h3_requested(a) & 255;
-    if (variant == 4 && !a.head_wh && bf_fused_block_h3v_supports(a.H, a.W)) return H3Kernel::FullRow;
-    return variant == 2 ? H3Kernel::Tiles16 : H3Kernel::Tiles32;
+    const int requested = a.variant >= 0 ? a.variant : (g_h3_variant >= 0 ? g_h3_variant : h3_default_variant(a));
+    const int variant = requested & 255;
+    H3Choice c;
+    c.bottom_up = (requested & 256) != 0;
+    if (variant == 4 && !a.head && bf_fused_block_h3v_supports(a.H, a.W)) c.kernel = H3Kernel::FullRow;
+    else c.kernel = variant == 2 ? H3Kernel::Tiles16 : H3Kernel::Tiles32;
+    return c;
 }
 
 template <class Cfg>
@@ -515,43 +514,48 @@ static hipError_t launch_h3(void (*kernel)(FusedH3Args), FusedH3Args a, hipStrea
     return hipGetLastError();
 }
 
-bool bf_fused_block_h3_is_streaming(const FusedH3Args& a) { return h3_select(a) == H3Kernel::FullRow; }
-
 // Two blocks per launch (fused_h3w.hip) beyond the shapes of the one-block streaming kernel: its 128-column strips take any image width,
 // and at two blocks per launch a band's fill is amortised earlier -- with the library's default selection, from 4 096 rows of strips per
 // forward on (B * H * ceil(W / 128)) consecutive blocks run two per launch; an odd block count runs its single block on whatever
-// bf_launch_fused_block_h3 picks.  Measured (tools/exp/regime_sweep.py, resnet 1x18, us per forward, pairs / 16 x 32 tiles):
+// bf_select_fused_block_h3 picks.  Measured (tools/exp/regime_sweep.py, resnet 1x18, us per forward, pairs / 16 x 32 tiles):
 // 8 x 256^2 403 / 429, 6 x 256^2 357 / 355, 2 x 512^2 404 / 424, 1 x 512^2 295 / 282, 32 x 128^2 397 / 420, 16 x 128^2 291 / 281,
 // 32 x 512^2 4 300 / 5 570, 1 x 1080 x 1920 2 207 / 2 747.
 // Images of fewer than 24 rows are the exception (a band's 12-step fill per handful of rows): 512 x 8 x 256 runs 830 us on the one-block
 // streaming kernel, 899 in pairs; 300 x 20 x 100 867 on tiles, 969 in pairs -- they keep the one-block selection of h3_default_variant.
 // A variant forced through set_option / bf_debug_set_h3_variant pairs exactly where it selects the streaming kernel (tests, A/B).
-bool bf_fused_block_h3_use_pairs(const FusedH3Args& a)
+bool bf_fused_block_h3_use_pairs(const H3Request& a)
 {
-    if (a.head_wh || a.compact) return false;
-    if (a.variant >= 0 || g_h3_variant >= 0) return bf_fused_block_h3_is_streaming(a);
+    if (a.head || a.compact) return false;
+    if (a.variant >= 0 || g_h3_variant >= 0) return bf_select_fused_block_h3(a).kernel == H3Kernel::FullRow;
     const int64_t nstrips = (a.W + 127) / 128;
     return a.W >= 1 && a.H >= 24 && (int64_t)a.B * a.H * nstrips >= 4096;
 }
 
-// name of the kernel bf_launch_fused_block_h3 launches for these arguments
-const char* bf_fused_block_h3_kernel_name(const FusedH3Args& a)
+const char* bf_fused_block_h3_kernel_name(H3Kernel k)
 {
-    return h3_select(a) == H3Kernel::FullRow ? "fused_block_h3v_kernel" : "fused_block_h3r_kernel";
+    return k == H3Kernel::FullRow ? "fused_block_h3v_kernel" : "fused_block_h3r_kernel";
 }
 
-hipError_t bf_launch_fused_block_h3(const FusedH3Args& args, hipStream_t s)
+// launches the kernel the caller chose (bf_select_fused_block_h3 with the arguments of THIS launch): nothing is chosen here
+hipError_t bf_launch_fused_block_h3_as(const FusedH3Args& args, H3Kernel k, hipStream_t s)
 {
     FusedH3Args a = args;
     if (!a.zeros || !a.dump) return hipErrorInvalidValue;
     if ((int64_t)a.H * a.W * 64 >= ((int64_t)1 << 32)) return hipErrorInvalidValue;      // 32-bit in-image offsets
-    if (h3_requested(a) & 256) a.reverse_tiles = 1;             // tests: the bottom-up walk of the full-row streaming kernel
-    const H3Kernel k = h3_select(a);
     if (k == H3Kernel::FullRow) return bf_launch_fused_block_h3v(a, s);
     if (a.compact) return hipErrorInvalidValue;                 // only the streaming kernel reads the compact layout
     if (k == H3Kernel::Tiles16) return launch_h3<H3Small>(fused_block_h3r_kernel<H3Small>, a, s);   // two 4-wave workgroups per CU
     if (a.head_wh) return launch_h3<H3Default>(fused_block_h3r_kernel<H3Default, 1>, a, s);
     return launch_h3<H3Default>(fused_block_h3r_kernel<H3Default>, a, s);
+}
+
+// handle-less callers (debug entries): select, then launch that
+hipError_t bf_launch_fused_block_h3(const FusedH3Args& args, hipStream_t s)
+{
+    FusedH3Args a = args;
+    const H3Choice c = bf_select_fused_block_h3({a.B, a.H, a.W, a.variant, a.head_wh != nullptr, a.compact != 0});
+    if (c.bottom_up) a.reverse_tiles = 1;                       // tests: the bottom-up walk of the full-row streaming kernel
+    return bf_launch_fused_block_h3_as(a, c.kernel, s);
 }
 
 // ------------------------------------------------------------------------------------------

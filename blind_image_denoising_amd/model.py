@@ -316,6 +316,15 @@ class HydraModel:
         name = self._lib.bf_get_block_kernel(self._h, C.byref(n))
         return (name.decode() if name else ""), int(n.value)
 
+    def forward_plan(self, batch: int, height: int, width: int, pad_pow2: bool = True):
+        """(the launches a forward of this shape would make with the options as they are, as one line of text; their number), from
+        the plan the forward itself runs (bf_debug_forward_plan, include/bfcnn_hip_debug.h has the grammar).  Needs no GPU."""
+        import ctypes as C
+        buf = C.create_string_buffer(1 << 14)
+        n = self._lib.bf_debug_forward_plan(self._h, int(batch), int(height), int(width), int(bool(pad_pow2)), buf, len(buf))
+        N.check(n if n < 0 else 0, self._h, "bf_debug_forward_plan")
+        return buf.value.decode(), int(n)
+
     # ---- execution -----------------------------------------------------------------------
     def _as_device(self, x, dtype):
         was_numpy = isinstance(x, np.ndarray)

@@ -676,7 +676,11 @@ int bf_set_option(bf_handle h, const char* key, int value);
  * the caller's stream (a ring of 256 pairs; setting the option again restarts the window); after the
  * caller has synchronised, this returns the SUM of the elapsed milliseconds of the brackets of all
  * forwards since the option was set (the last 256 at most) and the number of kernel launches inside
- * them (bench.py roofline: average launch duration over the timed region). */
+ * them (bench.py roofline: average launch duration over the timed region).
+ * bf_train_step uses the same ring with another meaning: one pair around every launch of its one-kernel block
+ * backward (bwd_block_h3t_kernel, where the step runs it).  A window holds pairs of ONE meaning: the first pair of the other
+ * kind restarts it, as setting the option does, so after a forward the figures are those of the forwards since the last
+ * training step, and after a training step those of the block-backward launches since the last forward. */
 int bf_get_timing(bf_handle h, float* ms, int* launches);
 /* name of the kernel that ran most of the residual-block launches of the handle's LAST forward ("" before the first one) and
  * the number of block launches that forward made: what a profile of the run must show, and the key bench.py looks counter

@@ -74,6 +74,25 @@ int bf_debug_bwd3x3_h3_grid_ex(int batch, int height, int width, int dbuf);
 int bf_debug_bwd3x3_h3(const float* x, const float* g, const float* c, const float* coef, const float* w_hwio, float* out,
                        const float* res, const float* bnc, float* dw, float* stats, float* scratch, int batch, int height,
                        int width, int epi, int reverse, int repack, void* stream);
+/* What a forward of `batch` images of height x width would launch on this handle, with its options as they are now (pad_pow2 = 1:
+   the sizes are first padded to powers of two, as bf_forward_u8 / bf_forward_u8_f32 do; 0: as bf_forward_f32).  Host arithmetic
+   only: no GPU is touched, and the forward itself runs from the same plan.  Returns the number of residual-block launches (what
+   bf_get_block_kernel reports after that forward) or a negative BF_E*; `out` receives one NUL-terminated line, and a line that does
+   not fit out_bytes is BF_EINVAL (out = ""), never a truncated one.
+     line   = layout { " " launch } [ " head" ]
+     layout = "f32" | "split" | "compact"          activations between the base convolution and the head: fp32 NHWC, split-planar
+                                                   f16 hi / lo, split-planar with fp8 lo planes
+     launch = kernel ":" blocks { "," mark }       one per kernel launch of the residual blocks, in launch order
+     kernel = "fused_block2_h3w_kernel" | "fused_block_h3v_kernel" | "fused_block_h3r_kernel" | "fused_block_v4_kernel" |
+              "conv3x3_c16_kernel"
+     blocks = i                                    the launch runs block i
+            | i "+" j                              ... blocks i and j = i + 1 (two per launch)
+            | i "." c                              ... convolution c of block i (a block run as one launch per convolution)
+     mark   = "t16"                                fused_block_h3r_kernel on 16 x 16 tiles (else 16 x 32)
+            | "rev"                                the launch walks its bands last to first
+            | "head"                               the launch also runs the head
+   in that order; the final " head" stands for the head kernel and is absent exactly when a launch is marked "head". */
+int bf_debug_forward_plan(bf_handle h, int batch, int height, int width, int pad_pow2, char* out, int out_bytes);
 int bf_debug_mfma_probe(const float* a, const float* b, float* d, void* stream);
 /* bf_upsample2x on C % 4 != 0 maps: 1 (default) the row-walking 16-byte kernel, 0 the 4-byte row kernel (same bits; A/B and tests) */
 int bf_debug_set_upsample_band(int on);

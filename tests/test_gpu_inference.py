@@ -575,3 +575,92 @@ def test_library_reports_the_block_kernel_it_launched():
     cfg3, spec3, params3, state3, m3 = _model(3, seed=3)       # odd count: the single block first, then a pair
     bf.DenoiserModule(m3)(big)
     assert m3.block_kernel() == ("fused_block2_h3w_kernel", 2)
+
+
+# ---- the forward runs what its plan says ------------------------------------------------------------------------------------------
+# (no_layers, convolutions per block, (B, H, W), options): (16, 256, 64) = 4 096 rows of one strip, the smallest shape of this file at
+# which the default selection runs two blocks per launch
+PLAN_CASES = {
+    "default-small": (4, 2, (2, 32, 32), {}),
+    "default-pairs": (4, 2, (16, 256, 64), {}),
+    "default-pairs-odd": (3, 2, (16, 256, 64), {}),
+    "h3_pair-0": (4, 2, (16, 256, 64), {"h3_pair": 0}),
+    "h3_pair_head": (4, 2, (16, 256, 64), {"h3_pair_head": 1}),
+    "fused_head": (4, 2, (16, 256, 64), {"fused_head": 1}),
+    "h3_compact": (4, 2, (16, 256, 64), {"h3_compact": 1}),
+    "arith-0": (4, 2, (16, 256, 64), {"arith": 0}),
+    "fused_blocks-0": (4, 2, (16, 256, 64), {"fused_blocks": 0}),
+    "block_convs-1": (4, 1, (2, 32, 32), {}),
+    "block_convs-3": (4, 3, (2, 32, 32), {}),
+}
+_plan_refs = {}
+
+
+def _plan_case(no_layers, nb, shape):
+    """model parts, batch and the oracle's first image of a plan case: computed once per (model, shape), shared, never modified"""
+    key = (no_layers, nb, shape)
+    if key not in _plan_refs:
+        cfg = O.canonical_config(no_layers=no_layers)
+        cfg["model"]["backbone"].update(block_kernels=[3] * nb, block_filters=[16] * nb)
+        spec = O.ResnetSpec.from_config(cfg["model"])
+        params, state = O.init_params(spec, seed=3, nontrivial_bn=True)
+        _, noisy = O.synthetic_batch(*shape, seed=2)
+        _plan_refs[key] = (cfg, params, state, noisy, O.denoiser_module_call(spec, params, state, noisy[:1]))
+    return _plan_refs[key]
+
+
+@pytest.mark.parametrize("case", list(PLAN_CASES))
+def test_forward_runs_what_its_plan_says(case):
+    """bf_debug_forward_plan before the forward, bf_get_block_kernel after it: the same dominant kernel and launch count (the CPU
+    tests hold the plan to the selection rule; this holds the forward to the plan), and the result to the oracle within one grey level.
+    The compact layout is held to the default layout's output of the same batch at the bar of test_compact_activation_layout."""
+    from test_host_and_cabi import _plan_totals
+    no_layers, nb, shape, options = PLAN_CASES[case]
+    cfg, params, state, noisy, ref = _plan_case(no_layers, nb, shape)
+    m = bf.model_builder(cfg["model"], device="cuda").hydra
+    m.set_weights(params, state)
+    x = noisy.astype(np.float32)
+    plain = np.asarray(m(x), np.float64) if "h3_compact" in options else None
+    for k, v in options.items():
+        m.set_option(k, v)
+    line, launches = m.forward_plan(*shape)
+    got = bf.DenoiserModule(m)(noisy)
+    assert m.block_kernel() == _plan_totals(line) and m.block_kernel()[1] == launches, (line, m.block_kernel())
+    if plain is None:
+        assert got.dtype == np.uint8 and np.abs(got[:1].astype(int) - ref.astype(int)).max() <= 1
+    else:
+        assert m.forward_plan(*shape, pad_pow2=False) == (line, launches)          # (powers of two: the float entry plans the same)
+        f = np.asarray(m(x), np.float64)
+        assert m.block_kernel() == _plan_totals(line)
+        assert np.isfinite(f).all() and not np.array_equal(f, plain) and np.abs(f - plain).mean() / 255.0 <= 5e-5
+
+
+def test_timing_window_holds_pairs_of_one_kind():
+    """bf_get_timing on a handle that times forwards AND training steps: a window holds the event pairs of one of them.  One pair
+    per forward around its block launches (two launches for four blocks here); one pair per bwd_block_h3t launch of a training step
+    (four blocks: four launches) -- the first pair of the other kind restarts the window, so neither report counts the other's pairs."""
+    import ctypes as C
+    from blind_image_denoising_amd import _native as N
+    cfg, spec, params, state, m = _model(4, seed=3)
+    fns = bf.build_train_functions(m, bf.loss_function_builder(cfg["loss"]))
+    _, big = O.synthetic_batch(16, 256, 64, seed=2)
+    clean, noisy = O.synthetic_batch(2, 16, 32, seed=5)       # the smallest shape tests/test_gpu_training.py runs train_bwd_block = 2 at
+    mod = bf.DenoiserModule(m)
+
+    def timing():
+        torch.cuda.synchronize()
+        ms, ln = C.c_float(), C.c_int()
+        N.check(N.lib().bf_get_timing(m._h, C.byref(ms), C.byref(ln)), m._h)
+        return float(ms.value), int(ln.value)
+
+    m.set_option("train_bwd_block", 2)
+    m.set_option("timing", 1)
+    mod(big)
+    assert timing()[1] == 2
+    fns.train_step_single_gpu(torch.from_numpy(clean.astype(np.float32)), torch.from_numpy(noisy.astype(np.float32)), (1.0,), 0.0, None)
+    assert "bwd_block_h3t_kernel" in N.lib().bf_get_train_kernels(m._h).decode()
+    ms, launches = timing()
+    assert launches == 4 and ms > 0.0                          # the forward's pair is gone
+    mod(big)
+    ms, launches = timing()
+    assert launches == 2 and ms > 0.0

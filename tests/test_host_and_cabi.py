@@ -207,6 +207,202 @@ def test_workspace_bytes_are_pinned():
         assert L.bf_workspace_bytes(m._h, N.BF_MODE_INFERENCE, B, H, W) == infer, (B, H, W)
 
 
+# ---- the forward plan (csrc/engine_infer.hip make_forward_plan, csrc/fused_h3.hip bf_select_fused_block_h3) -----------------------
+PLAN_OPTIONS = {"arith": 1, "fused_blocks": 1, "h3_pair": 1, "h3_pair_head": 0, "fused_head": 0, "h3_compact": 0, "h3_zigzag": 1,
+                "h3_variant": -1}           # the library's defaults
+
+
+def _h3_select(B, H, W, variant, head, compact):
+    """restatement of the one selection rule of a single split-f16 block: (kernel, 16 x 16 tiles, bottom-up walk forced)"""
+    streams = 1 <= W <= 256 and H >= 1 and not head                # the full-row streaming kernel: up to 256 columns, no head epilogue
+    if variant < 0:
+        tiles32 = B * -(-H // 16) * -(-W // 32)
+        if streams and B * H >= 3072 and (H >= 24 or W > 128):
+            variant = 4
+        else:
+            variant = 2 if (not head and not compact and tiles32 < 512 and tiles32 != 256) else 1
+    v = variant & 255
+    if v == 4 and streams:
+        return "fused_block_h3v_kernel", False, bool(variant & 256)
+    return "fused_block_h3r_kernel", v == 2, bool(variant & 256)
+
+
+def _forward_plan(no_layers, block_convs, head_fits, options, B, H, W):
+    """restatement of make_forward_plan + its printer for a model of `no_layers` blocks of `block_convs` convolutions whose head
+    is (not) linear with 3 channels, at the PADDED size H x W: (the line of bf_debug_forward_plan, block launches)"""
+    o = dict(PLAN_OPTIONS, **options)
+    N = no_layers
+    h3 = bool(o["fused_blocks"] and o["arith"] == 1 and N > 0 and block_convs == 2)
+    head_in_block = compact = pair_ok = head_in_pair = False
+    if h3:
+        head_in_block = bool(o["fused_head"]) and head_fits
+        plain = _h3_select(B, H, W, o["h3_variant"], False, False)
+        compact = bool(o["h3_compact"]) and not head_in_block and plain[0] == "fused_block_h3v_kernel"
+        if o["h3_pair"] and not compact:
+            if o["h3_pair"] == 2:
+                pair_ok = True
+            elif o["h3_variant"] >= 0:
+                pair_ok = plain[0] == "fused_block_h3v_kernel"
+            else:
+                pair_ok = H >= 24 and B * H * -(-W // 128) >= 4096
+        head_in_pair = pair_ok and not head_in_block and bool(o["h3_pair_head"]) and N >= 2 and head_fits
+    tokens, launches, i = [], 0, 0
+    while i < N:
+        zz = bool(o["h3_zigzag"]) and launches % 2 == 1
+        if pair_ok and i + 1 < N and not (head_in_block and i + 1 == N - 1) and not (i == 0 and N % 2 == 1):
+            marks = (["rev"] if zz else []) + (["head"] if head_in_pair and i + 2 == N else [])
+            tokens.append(",".join([f"fused_block2_h3w_kernel:{i}+{i + 1}"] + marks))
+            launches, i = launches + 1, i + 2
+            continue
+        if h3:
+            head = head_in_block and i == N - 1
+            name, t16, up = _h3_select(B, H, W, 1, True, False) if head else _h3_select(B, H, W, o["h3_variant"], False, compact)
+            marks = (["t16"] if t16 else []) + (["rev"] if zz or up else []) + (["head"] if head else [])
+            tokens.append(",".join([f"{name}:{i}"] + marks))
+            launches += 1
+        elif block_convs == 2 and o["fused_blocks"]:
+            tokens.append(f"fused_block_v4_kernel:{i}")
+            launches += 1
+        else:
+            tokens += [f"conv3x3_c16_kernel:{i}.{j}" for j in range(block_convs)] if block_convs != 1 else [f"conv3x3_c16_kernel:{i}"]
+            launches += block_convs
+        i += 1
+    layout = "compact" if compact else ("split" if h3 else "f32")
+    if not (head_in_block or head_in_pair):
+        tokens.append("head")
+    return " ".join([layout] + tokens), launches
+
+
+def _plan_totals(line):
+    """(the kernel that runs most blocks -- a launch counts for the blocks it runs, of equals the one met first --, block launches)
+    of a plan line: what bf_get_block_kernel reports after that forward"""
+    names = [t.split(":")[0] for t in line.split()[1:] if t != "head"]
+    weight = {}
+    for t, name in zip([t for t in line.split()[1:] if t != "head"], names):
+        weight[name] = weight.get(name, 0) + (2 if "+" in t else 1)
+    best = max(weight.values(), default=0)
+    return next((n for n in names if weight[n] == best), ""), len(names)
+
+
+def _plan_model(no_layers, block_convs=2, head_activation="linear", output_channels=3):
+    cfg = O.canonical_config(no_layers=no_layers)["model"]
+    cfg["backbone"].update(block_kernels=[3] * block_convs, block_filters=[16] * block_convs)
+    cfg["denoiser"].update(activation=head_activation, output_channels=output_channels)
+    N.lib().bf_debug_set_h3_variant(-1)          # the process-wide override of the handle-less entries is part of the rule: off
+    return bf.model_builder(cfg, device="cpu").hydra
+
+
+def _pow2(n):
+    return 1 << (n - 1).bit_length()
+
+
+@pytest.mark.parametrize("no_layers,shape,options,kernel,launches", [
+    (4, (2, 32, 32), {}, "fused_block_h3r_kernel", 4),
+    (4, (16, 256, 64), {}, "fused_block2_h3w_kernel", 2),
+    (4, (16, 256, 64), {"h3_pair": 0}, "fused_block_h3v_kernel", 4),
+    (4, (16, 256, 64), {"arith": 0}, "fused_block_v4_kernel", 4),
+    (3, (16, 256, 64), {}, "fused_block2_h3w_kernel", 2),
+    (2, (6, 352, 300), {}, "fused_block2_h3w_kernel", 1),
+    (3, (6, 352, 300), {}, "fused_block2_h3w_kernel", 2),
+    (2, (6, 352, 300), {"h3_pair": 0}, "fused_block_h3r_kernel", None),
+    (3, (6, 352, 300), {"h3_pair": 0}, "fused_block_h3r_kernel", None),
+    (2, (1, 64, 300), {}, "fused_block_h3r_kernel", None),
+    (3, (1, 64, 300), {}, "fused_block_h3r_kernel", None),
+    (2, (2, 64, 64), {"h3_variant": 4}, "fused_block2_h3w_kernel", 1),
+])
+def test_forward_plan_restatement_is_pinned_to_what_the_gpu_tests_assert(no_layers, shape, options, kernel, launches):
+    """the Python restatement of the selection rule, held first to the facts tests/test_gpu_inference.py asserts after real forwards
+    of the canonical model on the uint8 path (sizes padded to powers of two) -- and the library to the same facts"""
+    B, H, W = shape
+    line, n = _forward_plan(no_layers, 2, True, options, B, _pow2(H), _pow2(W))
+    assert _plan_totals(line) == (kernel, n) and (launches is None or n == launches), line
+    if no_layers == 3 and kernel == "fused_block2_h3w_kernel":
+        assert "+" not in line.split()[1] and "+" in line.split()[2]           # the single block is the first launch
+    m = _plan_model(no_layers)
+    for k, v in options.items():
+        m.set_option(k, v)
+    assert m.forward_plan(B, H, W) == (line, n)
+
+
+def _check_plan_structure(line, launches, no_layers, block_convs):
+    tokens = line.split()
+    assert tokens[0] in ("f32", "split", "compact")
+    runs = [t for t in tokens[1:] if t != "head"]
+    assert launches == len(runs)
+    seen, convs, carried = [], {}, 0
+    for k, t in enumerate(runs):
+        name, _, rest = t.partition(":")
+        blocks, *marks = rest.split(",")
+        assert marks == [mk for mk in ("t16", "rev", "head") if mk in marks], t          # known marks, once each, in order
+        if "+" in blocks:
+            a, b = map(int, blocks.split("+"))
+            assert b == a + 1 and name == "fused_block2_h3w_kernel" and tokens[0] == "split", t     # a pair never follows compact
+            seen += [a, b]
+        elif "." in blocks:
+            a, c = map(int, blocks.split("."))
+            assert name == "conv3x3_c16_kernel", t
+            convs.setdefault(a, []).append(c)
+            if c == 0:
+                seen.append(a)
+        else:
+            seen.append(int(blocks))
+        if "head" in marks:
+            carried += 1
+            assert k == len(runs) - 1, line                                               # only the last launch carries the head
+    assert seen == list(range(no_layers)), line                                           # every block once, in order
+    assert all(c == list(range(block_convs)) for c in convs.values()), line               # ... and each of its convolutions
+    assert carried <= 1 and (tokens[-1] == "head") == (carried == 0) and tokens.count("head") <= 1, line
+
+
+def test_forward_plan_matches_the_restatement_over_a_seeded_sweep():
+    """bf_debug_forward_plan -- the plan every forward runs from -- string for string against the restatement: depths 0..7 and 18,
+    1 / 2 / 3 convolutions per block, heads the folded forms cannot carry, every inference option at each of its values, padded and
+    unpadded sizes; and the structure every plan must have"""
+    rng = np.random.default_rng(4242)
+    values = {"arith": [0, 1], "fused_blocks": [0, 1], "h3_pair": [0, 1, 2], "h3_pair_head": [0, 1], "fused_head": [0, 1],
+              "h3_compact": [0, 1], "h3_zigzag": [0, 1], "h3_variant": [-1, 1, 2, 4, 4 | 256]}
+    models, pairs, compacts, carried = {}, 0, 0, 0
+    for draw in range(400):
+        no_layers = int(rng.choice([0, 1, 2, 3, 4, 5, 6, 7, 18]))
+        block_convs = int(rng.choice([1, 2, 2, 2, 2, 3]))
+        head = [("linear", 3), ("linear", 3), ("relu", 3), ("linear", 1)][int(rng.integers(4))]
+        key = (no_layers, block_convs) + head
+        if key not in models:
+            models[key] = _plan_model(*key)
+        m = models[key]
+        # most draws keep an option at its default, so that the interesting paths (pairs, compact) are reached often
+        options = {k: int(rng.choice(v)) if rng.random() < 0.4 else PLAN_OPTIONS[k] for k, v in values.items()}
+        for k, v in options.items():
+            m.set_option(k, v)
+        pad = bool(rng.integers(2))
+        big = rng.random() < 0.5                       # both sides of the row counts where the selection changes
+        H, W = int(rng.integers(1, 701)), int(rng.integers(1, 257 if rng.random() < 0.5 else 701))     # (256: the streaming kernel's width)
+        B = int(rng.integers(1, 161)) if big else int(rng.integers(1, 9))
+        got = m.forward_plan(B, H, W, pad_pow2=pad)
+        want = _forward_plan(no_layers, block_convs, head == ("linear", 3), options, B, _pow2(H) if pad else H, _pow2(W) if pad else W)
+        assert got == want, (draw, key, options, (B, H, W), pad)
+        _check_plan_structure(got[0], got[1], no_layers, block_convs)
+        pairs += "+" in got[0]
+        compacts += got[0].startswith("compact")
+        carried += ",head" in got[0]
+    assert pairs >= 40 and compacts >= 10 and carried >= 10, (pairs, compacts, carried)      # the sweep did reach those paths
+
+
+def test_forward_plan_error_cases():
+    m = _plan_model(4)
+    L = N.lib()
+    buf = C.create_string_buffer(b"x" * 63, 64)
+    assert L.bf_debug_forward_plan(None, 2, 32, 32, 1, buf, 64) == N.BF_EINVAL
+    line, n = m.forward_plan(2, 32, 32)
+    assert L.bf_debug_forward_plan(m._h, 2, 32, 32, 1, buf, 64) == N.BF_EINVAL and buf.value == b""     # too small: no truncated line
+    assert "does not fit" in N.last_error(m._h)
+    exact = C.create_string_buffer(len(line) + 1)
+    assert L.bf_debug_forward_plan(m._h, 2, 32, 32, 1, exact, len(line) + 1) == n and exact.value.decode() == line
+    assert L.bf_debug_forward_plan(m._h, 2, 32, 32, 1, exact, len(line)) == N.BF_EINVAL
+    assert L.bf_debug_forward_plan(m._h, 0, 32, 32, 1, buf, 64) == N.BF_EINVAL
+    assert L.bf_debug_forward_plan(m._h, 2, 32, 32, 1, None, 64) == N.BF_EINVAL
+
+
 def test_load_model_errors_mirror_reference():
     with pytest.raises(ValueError, match="cannot be empty"):
         bf.load_model("")
