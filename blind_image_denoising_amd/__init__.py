@@ -33,6 +33,8 @@ from .file_operations import load_image
 from . import metrics
 from .metrics import ImageMetrics, image_metrics, image_metric_sums, psnr, ssim, mae, evaluate
 from .noise_estimate import NoiseEstimate, noise_statistics, noise_summary, estimate_noise, evaluate_blind
+from . import risk
+from .risk import RiskEstimate, risk_probe_stack_u8, risk_sums, estimate_risk, evaluate_blind_risk, format_risk_report
 from . import regularizers
 from . import pruning
 from .pruning import (PruneStrategy, prune_function_builder, get_conv2d_weights, conv2d_sparsity, conv2d_ranges)

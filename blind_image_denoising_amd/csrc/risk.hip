@@ -1,0 +1,268 @@
+// Stein's unbiased risk estimate (SURE) around the denoiser: the two kernels that are not the denoiser.  For y = x + n,
+// n ~ N(0, sigma^2),  E |f(y) - x|^2 / N = E[ |f(y) - y|^2 / N - sigma^2 + (2 sigma^2 / N) div f(y) ], and the divergence comes
+// from a Monte-Carlo probe (Ramani, Blu, Unser 2008): div f(y) ~ b . (f(y + a b) - f(y)) / a with b = +-1 per element.
+//   bf_op_risk_probe_u8: one read of the uint8 batch, member 0 = the batch, member p = 1..K = the batch + a s_p;
+//   bf_op_risk_sums:     per image and channel  R = sum (f_0 - y)^2  and  D_p = sum s_p (f_p - f_0)  over the float results.
+// The host side is blind_image_denoising_amd/risk.py; the formulas and the assumptions are DESIGN.md 7.8.
+//
+// Probe sign.  Element e = (h W + w) C + c of an image (image-local: every image of a batch gets the same signs, so an image
+// gets the same bits alone or inside a batch) belongs to Philox group j = e >> 2 and takes word i = e & 3 of
+// philox4x32_10(counter = (lo32 j, hi32 j, p, 2), key = (lo32 seed, hi32 seed)): s = +1 when bit 31 of the word is set, else -1,
+// and s = -s when y + a s leaves 0..255 (reflected at the range ends: in range for every amplitude the entries accept).  The signs
+// are never stored: the sums kernel regenerates them from (seed, p, e, y).
+//
+// Layout.  Both kernels index an image by its flat element, four consecutive elements (one Philox call, one dword of uint8, one
+// float4) per step, so the lanes of a wave touch consecutive addresses.  The dword / float4 accesses need an image stride of a
+// multiple of four elements and aligned bases; every other shape takes byte / float accesses of the same elements.
+//   probe: a thread owns one group.
+//   sums:  a thread owns RkUnit<C>::T "units" of lcm(4, C) elements, 256 units apart, so that the channel of each of its elements
+//          is a compile-time constant; it keeps y and f_0 of its units in registers and walks the probes over them.
+// Reduction in a fixed order, as metrics.hip: per thread in ascending element order, wave shuffle, LDS over the four waves, one
+// partial per workgroup and quantity in scratch, then one workgroup per image.  Every term is formed in fp64 from the fp32 and
+// uint8 values.  The grid of an image depends on its shape alone: two calls return the same bits, and an image inside a batch
+// the bits of that image alone.  There are no atomics.
+#include "bf_common.h"
+#include "philox.h"
+
+namespace {
+
+constexpr int RK_MAXC = 4, RK_MAXK = 8, RK_MAXA = 16;
+constexpr int RK_THREADS = 256;
+constexpr int RK_MAXQ = RK_MAXC * (1 + RK_MAXK);          // quantities per image: [C][1 + K]
+
+// four probe signs of group j (bit i set: +1 for element 4 j + i), before the reflection
+__device__ __forceinline__ unsigned rk_sign_bits(int64_t j, int p, uint64_t seed)
+{
+    uint32_t r[4];
+    philox4x32_10((uint32_t)j, (uint32_t)((uint64_t)j >> 32), (uint32_t)p, 2u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    return (r[0] >> 31) | (r[1] >> 31) << 1 | (r[2] >> 31) << 2 | (r[3] >> 31) << 3;
+}
+
+// y + a s with the reflection: (the probed value, whether s = +1)
+__device__ __forceinline__ int rk_probe(int y, int a, bool plus, bool& up)
+{
+    int v = plus ? y + a : y - a;
+    up = plus;
+    if (v < 0 || v > 255) { v = plus ? y - a : y + a; up = !plus; }
+    return v;
+}
+
+// the four bytes of group j of an image of n elements, packed little-endian; bytes past the image are 0
+__device__ __forceinline__ unsigned rk_load_u8x4(const uint8_t* __restrict__ img, int64_t e, int64_t n, bool vec)
+{
+    if (e >= n) return 0u;
+    if (vec) return *reinterpret_cast<const unsigned*>(img + e);
+    unsigned v = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (e + i < n) v |= (unsigned)img[e + i] << (8 * i);
+    return v;
+}
+
+__device__ __forceinline__ void rk_load_f32x4(const float* __restrict__ img, int64_t e, int64_t n, bool vec, float (&v)[4])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = 0.f;
+    if (e >= n) return;
+    if (vec) {
+        const float4 q = *reinterpret_cast<const float4*>(img + e);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (e + i < n) v[i] = img[e + i];
+}
+
+// dst[(m B + b) n + e], m = 0..K: member 0 = src, member p = src + a s_p.  One thread per group of four elements.
+__global__ __launch_bounds__(RK_THREADS) void risk_probe_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int B,
+                                                                   int64_t n, int groups_x, int K, int a, uint64_t seed, int vec)
+{
+    const int b = blockIdx.x / groups_x;
+    const int64_t j = (int64_t)(blockIdx.x % groups_x) * RK_THREADS + threadIdx.x, e = 4 * j;
+    if (e >= n) return;
+    const unsigned y4 = rk_load_u8x4(src + (int64_t)b * n, e, n, vec);
+    for (int m = 0; m <= K; ++m) {
+        unsigned v4 = y4;
+        if (m > 0) {
+            const unsigned bits = rk_sign_bits(j, m, seed);
+            v4 = 0u;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                bool up;
+                v4 |= (unsigned)rk_probe((int)(y4 >> (8 * i) & 255u), a, bits >> i & 1u, up) << (8 * i);
+            }
+        }
+        uint8_t* __restrict__ d = dst + ((int64_t)m * B + b) * n + e;          // e + i < n below: inside member m, image b
+        if (vec) *reinterpret_cast<unsigned*>(d) = v4;
+        else
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (e + i < n) d[i] = (uint8_t)(v4 >> (8 * i));
+    }
+}
+
+template <int C> struct RkUnit {
+    static constexpr int GROUPS = C == 3 ? 3 : 1;        // lcm(4, C) / 4 Philox groups: a unit starts on channel 0
+    static constexpr int T = C == 3 ? 2 : 4;             // units per thread: 24 / 16 elements
+    static constexpr int ELEMS = GROUPS * 4;
+    static constexpr int TILE_UNITS = RK_THREADS * T;    // of a workgroup
+};
+
+int64_t rk_tiles(int64_t n, int C)
+{
+    const int64_t unit = C == 3 ? RkUnit<3>::ELEMS : RkUnit<1>::ELEMS, tile = C == 3 ? RkUnit<3>::TILE_UNITS : RkUnit<1>::TILE_UNITS;
+    const int64_t units = (n + unit - 1) / unit;
+    return (units + tile - 1) / tile;
+}
+
+// partial[workgroup][c][0] = sum (f_0 - y)^2, partial[workgroup][c][p] = sum s_p (f_p - f_0) over the tile's elements of channel c
+template <int C>
+__global__ __launch_bounds__(RK_THREADS) void risk_sums_tile_kernel(const uint8_t* __restrict__ y, const float* __restrict__ f, int B,
+                                                                    int64_t n, int tiles, int K, int a, uint64_t seed, int vec,
+                                                                    double* __restrict__ partial)
+{
+    using U = RkUnit<C>;
+    __shared__ double red[4][RK_MAXQ];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    const uint8_t* __restrict__ yb = y + (int64_t)b * n;
+
+    unsigned y4[U::T][U::GROUPS];
+    float f0[U::T][U::GROUPS][4];
+    double acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = 0.0;
+    const float* __restrict__ fb = f + (int64_t)b * n;
+#pragma unroll
+    for (int t = 0; t < U::T; ++t) {
+        const int64_t u = (int64_t)tile * U::TILE_UNITS + t * RK_THREADS + threadIdx.x;
+#pragma unroll
+        for (int g = 0; g < U::GROUPS; ++g) {
+            const int64_t e = (u * U::GROUPS + g) * 4;                      // loads are guarded by e (+ i) < n
+            y4[t][g] = rk_load_u8x4(yb, e, n, vec);
+            rk_load_f32x4(fb, e, n, vec, f0[t][g]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const double d = (double)f0[t][g][i] - (double)(y4[t][g] >> (8 * i) & 255u);       // 0 - 0 past the image
+                acc[(g * 4 + i) % C] += d * d;
+            }
+        }
+    }
+
+    for (int p = 0; p <= K; ++p) {
+        if (p > 0) {
+            const float* __restrict__ fp = f + ((int64_t)p * B + b) * n;
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = 0.0;
+#pragma unroll
+            for (int t = 0; t < U::T; ++t) {
+                const int64_t u = (int64_t)tile * U::TILE_UNITS + t * RK_THREADS + threadIdx.x;
+#pragma unroll
+                for (int g = 0; g < U::GROUPS; ++g) {
+                    const int64_t j = u * U::GROUPS + g;
+                    float v[4];
+                    rk_load_f32x4(fp, 4 * j, n, vec, v);
+                    const unsigned bits = rk_sign_bits(j, p, seed);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        bool up;
+                        rk_probe((int)(y4[t][g] >> (8 * i) & 255u), a, bits >> i & 1u, up);
+                        const double d = (double)v[i] - (double)f0[t][g][i];
+                        acc[(g * 4 + i) % C] += up ? d : -d;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            double w = acc[c];
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) w += __shfl_xor(w, m);
+            if (lane == 0) red[wave][c * (1 + K) + p] = w;
+        }
+    }
+    __syncthreads();
+    const int Q = C * (1 + K);
+    if ((int)threadIdx.x < Q)
+        partial[(int64_t)blockIdx.x * Q + threadIdx.x] =
+            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// out[image][c][q] = the partials of the image's workgroups added in a fixed order; one workgroup per image
+__global__ __launch_bounds__(RK_THREADS) void risk_sums_finalize_kernel(const double* __restrict__ partial, int tiles, int Q,
+                                                                        double* __restrict__ out)
+{
+    __shared__ double red[RK_THREADS];
+    const double* p = partial + (int64_t)blockIdx.x * tiles * Q;
+    for (int q = 0; q < Q; ++q) {
+        double acc = 0.0;
+        for (int i = threadIdx.x; i < tiles; i += RK_THREADS) acc += p[(int64_t)i * Q + q];
+        red[threadIdx.x] = acc;
+        __syncthreads();
+        for (int st = RK_THREADS / 2; st > 0; st >>= 1) {
+            if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[(int64_t)blockIdx.x * Q + q] = red[0];
+        __syncthreads();
+    }
+}
+
+// elements of an image, or 0 for a shape, probe count or amplitude the entries refuse
+int64_t rk_checked_elements(int B, int H, int W, int C, int probes, int amplitude)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || C < 1 || C > RK_MAXC || probes < 1 || probes > RK_MAXK || amplitude < 1 || amplitude > RK_MAXA)
+        return 0;
+    const int64_t n = (int64_t)H * W * C;
+    if (n > INT32_MAX - 4096) return 0;
+    const int64_t groups_x = ((n + 3) / 4 + RK_THREADS - 1) / RK_THREADS;
+    if (groups_x * B > INT32_MAX || rk_tiles(n, C) * B > INT32_MAX) return 0;
+    return n;
+}
+
+}  // namespace
+
+extern "C" int bf_op_risk_probe_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int probes, int amplitude,
+                                   uint64_t seed, void* stream)
+{
+    const int64_t n = rk_checked_elements(B, H, W, C, probes, amplitude);
+    if (!src || !dst || src == dst || n == 0) return BF_EINVAL;
+    const int groups_x = (int)(((n + 3) / 4 + RK_THREADS - 1) / RK_THREADS);
+    const int vec = n % 4 == 0 && ((uintptr_t)src | (uintptr_t)dst) % 4 == 0;
+    hipLaunchKernelGGL(risk_probe_u8_kernel, dim3((unsigned)(groups_x * B)), dim3(RK_THREADS), 0, (hipStream_t)stream, src, dst, B, n,
+                       groups_x, probes, amplitude, seed, vec);
+    return hipGetLastError() == hipSuccess ? BF_OK : BF_EHIP;
+}
+
+extern "C" int64_t bf_op_risk_sums_scratch_bytes(int B, int H, int W, int C, int probes)
+{
+    const int64_t n = rk_checked_elements(B, H, W, C, probes, 1);
+    if (n == 0) return BF_EINVAL;
+    return rk_tiles(n, C) * B * C * (1 + probes) * (int64_t)sizeof(double);
+}
+
+extern "C" int bf_op_risk_sums(const uint8_t* y, const float* f, int B, int H, int W, int C, int probes, int amplitude, uint64_t seed,
+                               void* scratch, int64_t scratch_bytes, double* out, void* stream)
+{
+    const int64_t n = rk_checked_elements(B, H, W, C, probes, amplitude);
+    if (!y || !f || !scratch || !out || n == 0) return BF_EINVAL;
+    if (scratch_bytes < bf_op_risk_sums_scratch_bytes(B, H, W, C, probes) || ((uintptr_t)scratch | (uintptr_t)out) % 8 || (uintptr_t)f % 4)
+        return BF_EINVAL;
+    const int tiles = (int)rk_tiles(n, C);
+    const int vec = n % 4 == 0 && (uintptr_t)y % 4 == 0 && (uintptr_t)f % 16 == 0;
+    const dim3 grid((unsigned)(tiles * B));
+    hipStream_t s = (hipStream_t)stream;
+    double* partial = (double*)scratch;
+#define RK_LAUNCH(CH)                                                                                                             \
+    hipLaunchKernelGGL(risk_sums_tile_kernel<CH>, grid, dim3(RK_THREADS), 0, s, y, f, B, n, tiles, probes, amplitude, seed, vec, partial)
+    switch (C) {
+    case 1: RK_LAUNCH(1); break;
+    case 2: RK_LAUNCH(2); break;
+    case 3: RK_LAUNCH(3); break;
+    default: RK_LAUNCH(4); break;
+    }
+#undef RK_LAUNCH
+    hipLaunchKernelGGL(risk_sums_finalize_kernel, dim3(B), dim3(RK_THREADS), 0, s, partial, tiles, C * (1 + probes), out);
+    return hipGetLastError() == hipSuccess ? BF_OK : BF_EHIP;
+}

@@ -1,0 +1,286 @@
+"""
+Stein's unbiased risk estimate (SURE): the mean squared error and PSNR of a denoiser on images that have no clean counterpart.
+
+For y = x + n with n ~ N(0, sigma^2) and N samples,
+
+    E |f(y) - x|^2 / N  =  E[ |f(y) - y|^2 / N  -  sigma^2  +  (2 sigma^2 / N) div f(y) ]
+
+and the divergence comes from a Monte-Carlo probe (Ramani, Blu, Unser, "Monte-Carlo SURE", 2008): div f(y) ~ s . (f(y + a s) -
+f(y)) / a with s = +-1 per sample.  Two kernels of csrc/risk.hip carry everything that is not the denoiser: `bf_op_risk_probe_u8`
+(one read of the uint8 batch; member 0 = the batch, member p = the batch + a s_p) and `bf_op_risk_sums` (per image and channel
+R = sum (f_0 - y)^2 and D_p = sum s_p (f_p - f_0), in fp64, in a fixed order).  Everything stays uint8 on the input side -- the
+amplitude `a` is a whole number of grey levels -- so every model family runs its usual fused uint8 -> float32 forward, once, on
+the [(1 + K) B, H, W, C] stack.
+
+The estimate is only as good as its assumptions: the noise is additive, white and Gaussian, and sigma is right (by default it
+comes from `noise_statistics`, an estimator).  Saturated samples violate both and are reflected, not perturbed, by the probe; the
+clipped fraction is therefore reported next to the number (`evaluate_blind_risk`).  DESIGN.md 7.8 has the details.
+"""
+from collections import namedtuple
+from typing import Dict, Iterable
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .metrics import _module_device
+from .module_denoiser import DenoiserModule, GraphedDenoiserModule
+from .noise_estimate import METHODS, _check_noisy_batch, _checked_method, noise_statistics
+from .self_ensemble import SelfEnsembleDenoiserModule
+
+RiskEstimate = namedtuple("RiskEstimate", ["mse", "psnr", "sigma", "residual_rms", "divergence", "probe_spread", "sums"])
+
+MAX_PROBES, MAX_AMPLITUDE = 8, 16
+
+
+def _checked_probe(probes, amplitude, seed):
+    for value, what, top in ((probes, "probes", MAX_PROBES), (amplitude, "amplitude", MAX_AMPLITUDE)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= top:
+            raise ValueError(f"{what} must be an int in 1..{top}, got {value!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed must be an int in 0..2^64-1, got {seed!r}")
+    return int(probes), int(amplitude), int(seed)
+
+
+def _require_tensor(t, dtype, what: str):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 4:
+        raise ValueError(f"{what} must be a {dtype} tensor of shape [B,H,W,C], got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if not 1 <= t.shape[3] <= 4:
+        raise ValueError(f"{what} must have 1..4 channels, got {tuple(t.shape)}")
+    if t.shape[0] < 1 or t.shape[1] < 1 or t.shape[2] < 1:
+        raise ValueError(f"{what} must not be empty, got {tuple(t.shape)}")
+
+
+def _require_device(t, dtype, what: str):
+    _require_tensor(t, dtype, what)
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} must live on the GPU: the risk kernels have no CPU execution path")
+
+
+def risk_probe_stack_u8(image_u8: torch.Tensor, probes: int = 1, amplitude: int = 1, seed: int = 0) -> torch.Tensor:
+    """bf_op_risk_probe_u8 on a uint8 device tensor [B,H,W,C] (C in 1..4): uint8 [(1 + probes) B, H, W, C], member-major; member 0
+    is the image, member p = 1..probes the image + amplitude * s_p, s_p = +-1 per sample from Philox (seed, p, sample index),
+    reflected where it would leave 0..255.  The signs of an image do not depend on its place in the batch."""
+    probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
+    _require_device(image_u8, torch.uint8, "image_u8")
+    image_u8 = image_u8.contiguous()
+    B, H, W, C = image_u8.shape
+    stack = torch.empty(((1 + probes) * B, H, W, C), dtype=torch.uint8, device=image_u8.device)
+    N.call("bf_op_risk_probe_u8", N.ptr(image_u8), N.ptr(stack), B, H, W, C, probes, amplitude, seed, N.stream_ptr(image_u8))
+    return stack
+
+
+def risk_sums(image_u8: torch.Tensor, stack_f32: torch.Tensor, probes: int, amplitude: int, seed: int) -> torch.Tensor:
+    """bf_op_risk_sums: float64 [B, C, 1 + probes] on the device.  [..., 0] = sum over the pixels of (f_0 - y)^2, [..., p] = sum of
+    s_p (f_p - f_0), for y = image_u8 [B,H,W,C] and f = stack_f32, the float32 result [(1 + probes) B, H, W, C] for
+    risk_probe_stack_u8(image_u8, probes, amplitude, seed); the signs are regenerated, not read.  fp64 terms, fixed order."""
+    probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
+    _require_tensor(image_u8, torch.uint8, "image_u8")
+    _require_tensor(stack_f32, torch.float32, "stack_f32")
+    _require_device(image_u8, torch.uint8, "image_u8")
+    B, H, W, C = image_u8.shape
+    if tuple(stack_f32.shape) != ((1 + probes) * B, H, W, C) or stack_f32.device != image_u8.device:
+        raise ValueError(f"stack_f32 must be {((1 + probes) * B, H, W, C)} on {image_u8.device} for {probes} probes of a "
+                         f"{tuple(image_u8.shape)} batch, got {tuple(stack_f32.shape)} on {stack_f32.device}")
+    image_u8, stack_f32 = image_u8.contiguous(), stack_f32.contiguous()
+    lib = N.lib()
+    nbytes = lib.bf_op_risk_sums_scratch_bytes(B, H, W, C, probes)
+    if nbytes < 0:
+        N.check(int(nbytes), None, "bf_op_risk_sums_scratch_bytes")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=image_u8.device)
+    out = torch.empty((B, C, 1 + probes), dtype=torch.float64, device=image_u8.device)
+    N.call("bf_op_risk_sums", N.ptr(image_u8), N.ptr(stack_f32), B, H, W, C, probes, amplitude, seed, N.ptr(scratch), nbytes,
+           N.ptr(out), N.stream_ptr(image_u8))
+    return out
+
+
+def risk_from_sums(sums, sigma, height: int, width: int, amplitude: int) -> RiskEstimate:
+    """The host formula, on what bf_op_risk_sums leaves.  `sums`: float64 [B, C, 1 + K] (R_c, D_1c .. D_Kc); `sigma`: float64
+    [B, C].  torch tensors (any device) or NumPy arrays; the result is of the same kind.  With HW = height * width:
+
+        div_c = mean_p(D_pc) / a                     mse_c = R_c / HW - sigma_c^2 + 2 sigma_c^2 (div_c / HW)
+        mse = mean_c mse_c                           psnr = 10 log10(255^2 / mse), +inf where mse <= 0
+        residual_rms = sqrt(mean_c R_c / HW)         divergence = mean_c div_c / HW
+        probe_spread = the sample standard deviation (n - 1) over the probes of the mse each probe gives alone; NaN for K = 1"""
+    was_numpy = isinstance(sums, np.ndarray)
+    s = torch.as_tensor(sums, dtype=torch.float64)
+    sg = torch.as_tensor(sigma, dtype=torch.float64).to(s.device)
+    if s.dim() != 3 or s.shape[2] < 2 or tuple(sg.shape) != tuple(s.shape[:2]):
+        raise ValueError(f"sums must be [B, C, 1 + K] and sigma [B, C], got {tuple(s.shape)} and {tuple(sg.shape)}")
+    C, K = s.shape[1], s.shape[2] - 1
+    hw, a = float(int(height) * int(width)), float(amplitude)
+    var = sg * sg
+    fit = s[:, :, 0] / hw                                             # [B, C]
+    div_p = s[:, :, 1:] / a / hw                                      # [B, C, K] divergence per sample, per probe
+    div_c = s[:, :, 1:].sum(dim=2) / float(K) / a / hw                # [B, C]
+    mse = (fit - var + 2.0 * var * div_c).sum(dim=1) / float(C)
+    mse_p = (fit.unsqueeze(2) - var.unsqueeze(2) + 2.0 * var.unsqueeze(2) * div_p).sum(dim=1) / float(C)       # [B, K]
+    if K > 1:
+        spread = torch.sqrt(((mse_p - mse_p.mean(dim=1, keepdim=True)) ** 2).sum(dim=1) / float(K - 1))
+    else:
+        spread = torch.full_like(mse, float("nan"))
+    psnr = torch.where(mse > 0.0, 10.0 * torch.log10(255.0 ** 2 / mse.clamp_min(1e-300)), torch.full_like(mse, float("inf")))
+    est = RiskEstimate(mse, psnr, sg, torch.sqrt(fit.sum(dim=1) / float(C)), div_c.sum(dim=1) / float(C), spread, s)
+    return RiskEstimate(*(v.cpu().numpy() for v in est)) if was_numpy else est
+
+
+def _float_callable(module):
+    """the float32 form of `module`: uint8 [B,H,W,C] device tensor -> float32 of the same shape, not rounded"""
+    if isinstance(module, GraphedDenoiserModule):
+        module = module._module                                  # the wrapped module, called directly
+    if isinstance(module, SelfEnsembleDenoiserModule):
+        return SelfEnsembleDenoiserModule(module._module, module.transforms, cast_to_uint8=False)
+    if isinstance(module, DenoiserModule):
+        inner = DenoiserModule(module.model_hydra, cast_to_uint8=False)
+        inner._deferred = module._deferred                       # one record of pending status words: module.check_status() sees this call
+        return inner
+    if not callable(module):
+        raise ValueError("module must be a DenoiserModule, GraphedDenoiserModule, SelfEnsembleDenoiserModule or a callable "
+                         "uint8 [B,H,W,C] -> float32 [B,H,W,C]")
+    return module
+
+
+def _checked_noisy(noisy):
+    was_numpy = isinstance(noisy, np.ndarray)
+    t = torch.from_numpy(np.ascontiguousarray(noisy)) if was_numpy else noisy
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4:
+        raise ValueError(f"noisy must be a uint8 [B,H,W,C] tensor or array, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if not 1 <= t.shape[3] <= 4 or t.shape[1] < 1 or t.shape[2] < 1:
+        raise ValueError(f"noisy must be [B,H,W,C] with H, W >= 1 and 1..4 channels, got {tuple(t.shape)}")
+    return t, was_numpy
+
+
+def _checked_sigma(sigma, B: int, C: int):
+    """None, or sigma as a float64 [B, C] host-or-device tensor (a float, [C] or [B, C] was given)"""
+    if sigma is None:
+        return None
+    try:
+        s = torch.as_tensor(sigma).to(torch.float64)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"sigma must be None, a float, a [C] or a [B, C] array, got {type(sigma)}") from None
+    if s.dim() == 0:
+        s = s.reshape(1, 1).expand(B, C)
+    elif tuple(s.shape) == (C,):
+        s = s.reshape(1, C).expand(B, C)
+    elif tuple(s.shape) != (B, C):
+        raise ValueError(f"sigma must be a float, [{C}] or [{B}, {C}] for this batch, got {tuple(s.shape)}")
+    if s.numel() and not bool((torch.isfinite(s) & (s >= 0)).all()):
+        raise ValueError("sigma must be finite and non-negative")
+    return s.contiguous()
+
+
+def _estimate(fn, noisy: torch.Tensor, sigma, method: str, probes: int, amplitude: int, seed: int) -> RiskEstimate:
+    """estimate_risk on a checked, non-empty device batch with the float form of the module"""
+    B, H, W, C = noisy.shape
+    stack = risk_probe_stack_u8(noisy, probes, amplitude, seed)
+    result = fn(stack)                                           # ONE call on [(1 + K) B, H, W, C]
+    if isinstance(result, torch.Tensor) and result.dtype == torch.uint8:
+        raise ValueError("the module returned uint8: a rounded output cannot carry the finite difference of the probe; "
+                         "pass a module that returns float32 (DenoiserModule(hydra, cast_to_uint8=False))")
+    if not isinstance(result, torch.Tensor) or result.dtype != torch.float32 or result.shape != stack.shape:
+        raise ValueError(f"the module returned {getattr(result, 'dtype', type(result))} {tuple(getattr(result, 'shape', ()))} "
+                         f"for a uint8 {tuple(stack.shape)} batch; float32 of the same shape is needed")
+    sums = risk_sums(noisy, result.to(noisy.device), probes, amplitude, seed)
+    if sigma is None:
+        sigma = noise_statistics(noisy)[:, :, 2 if method == "mad" else 1]
+    return risk_from_sums(sums, sigma.to(noisy.device), H, W, amplitude)
+
+
+def estimate_risk(module, noisy, sigma=None, method: str = "mad", probes: int = 1, amplitude: int = 1, seed: int = 0) -> RiskEstimate:
+    """The SURE estimate of the mean squared error between module(noisy) and the clean images nobody has, per image of the uint8
+    [B,H,W,C] batch `noisy` (torch or NumPy; NumPy is uploaded).  Returns RiskEstimate(mse [B], psnr [B], sigma [B,C], residual_rms
+    [B], divergence [B], probe_spread [B], sums [B,C,1+probes]) -- the formulas are risk_from_sums' -- as float64 tensors on the
+    batch's device, or NumPy arrays for a NumPy batch.
+
+    `sigma`: the noise standard deviation in grey levels: a float, [C] or [B,C]; None takes noise_statistics(noisy), column
+    `method` ("mad" or "immerkaer"; needs H, W >= 3).  `probes` (1..8) probes of `amplitude` (1..16) grey levels are averaged;
+    `seed` selects their signs (an image gets the same signs alone or inside a batch).
+
+    `module`: a DenoiserModule (run through DenoiserModule(hydra, cast_to_uint8=False), its status record shared, so that
+    module.check_status() covers the call), a SelfEnsembleDenoiserModule (rebuilt with cast_to_uint8=False over the same module
+    and transforms), a GraphedDenoiserModule (its wrapped module, called directly), or any callable that maps a uint8 device
+    tensor [B,H,W,C] to float32 of the same shape; a uint8 result raises ValueError.  A call is: probe stack, ONE module call on
+    [(1 + probes) B, H, W, C], sums.  An empty batch returns empty results without a launch.
+
+    The estimate inherits the arithmetic of the module: D is a difference of two forwards that differ by `amplitude` grey levels,
+    so forward rounding enters it relative to that difference (DESIGN.md 7.8 has the measured sizes for the split-f16 and the
+    exact-fp32 kernels; on the case measured there the two paths agree on the estimated mse to well below 1 %)."""
+    probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
+    method = _checked_method(method)
+    fn = _float_callable(module)
+    noisy, was_numpy = _checked_noisy(noisy)
+    B, H, W, C = noisy.shape
+    sigma = _checked_sigma(sigma, B, C)
+    if B == 0:
+        empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=noisy.device)
+        est = RiskEstimate(empty(0), empty(0), empty(0, C), empty(0), empty(0), empty(0), empty(0, C, 1 + probes))
+    else:
+        if was_numpy or not noisy.is_cuda:
+            if not was_numpy:
+                raise RuntimeError("noisy must live on the GPU (or be a NumPy array, which is uploaded): the risk kernels have no "
+                                   "CPU execution path")
+            noisy = noisy.to(_module_device(module))
+        est = _estimate(fn, noisy.contiguous(), sigma, method, probes, amplitude, seed)
+    return RiskEstimate(*(v.cpu().numpy() for v in est)) if was_numpy else est
+
+
+# ---- evaluation without ground truth -------------------------------------------------------------
+
+_KEYS = ("mse", "psnr", "sigma_in", "divergence", "clipped_fraction")
+
+
+def evaluate_blind_risk(module, noisy_batches: Iterable, sigma=None, method: str = "mad", probes: int = 1, amplitude: int = 1,
+                        seed: int = 0) -> Dict:
+    """evaluate_blind with a quality number: the SURE estimate of a denoiser on images that are already noisy.  `module` and the
+    other arguments as estimate_risk (`sigma`: None or a float for every batch); `noisy_batches`: an iterable of uint8 batches,
+    host or device, of any shapes (H, W >= 3).  Batch k is probed with seed + k.  Returns {"method", "probes", "amplitude",
+    "images", "batches": [one dict per batch], "aggregate": the same keys over every image}: the means over the images of the
+    estimated mse and psnr, sigma_in (the root mean square over the channels of the sigma that entered the estimate), divergence
+    (per sample) and clipped_fraction, the share of saturated input samples -- those violate the assumptions of the estimate.
+    Nothing is asserted; the module's deferred f16-range status is checked once at the end."""
+    probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
+    method = _checked_method(method)
+    fn = _float_callable(module)
+    if sigma is not None and (isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating))
+                              or not np.isfinite(sigma) or sigma < 0):
+        raise ValueError(f"sigma must be None or a non-negative float, got {sigma!r}")
+    batches = [_check_noisy_batch(b) for b in noisy_batches]
+    if not batches:
+        raise ValueError("no noisy batches to evaluate on")
+    dev = _module_device(module)
+    per_image = []                                               # one [5, B] device tensor per batch, rows as _KEYS
+    for k, noisy in enumerate(batches):
+        noisy = noisy.to(dev).contiguous()
+        B, H, W, C = noisy.shape
+        stats = noise_statistics(noisy)
+        sg = stats[:, :, 2 if method == "mad" else 1] if sigma is None else _checked_sigma(float(sigma), B, C)
+        est = _estimate(fn, noisy, sg, method, probes, amplitude, (seed + k) % 2 ** 64)
+        sigma_in = torch.sqrt((est.sigma * est.sigma).sum(dim=1) / float(C))
+        per_image.append(torch.stack([est.mse, est.psnr, sigma_in, est.divergence, stats[:, :, 3].sum(dim=1) / float(H * W * C)]))
+    if hasattr(module, "check_status"):
+        module.check_status()                                    # an overflow of the split-f16 kernels is not averaged into a number
+    rows = []
+    with np.errstate(invalid="ignore"):
+        host = [p.cpu().numpy() for p in per_image]
+        for noisy, h in zip(batches, host):
+            rows.append({"shape": [int(v) for v in noisy.shape], "images": int(h.shape[1]), **{k: float(h[i].mean()) for i, k in enumerate(_KEYS)}})
+        every = np.concatenate(host, axis=1)
+        aggregate = {"images": int(every.shape[1]), **{k: float(every[i].mean()) for i, k in enumerate(_KEYS)}}
+    return {"method": method if sigma is None else "given", "probes": probes, "amplitude": amplitude, "images": aggregate["images"],
+            "batches": rows, "aggregate": aggregate}
+
+
+def format_risk_report(report: Dict) -> str:
+    """the table tools/evaluate_risk.py prints"""
+    lines = [f"sigma: {report['method']}; {report['probes']} probe(s) of amplitude {report['amplitude']}",
+             "batch            shape  images   sigma in   estimated mse   estimated psnr   divergence   clipped"]
+
+    def line(name, shape, r):
+        return (f"{name:>5}  {shape:>15}  {r['images']:6d}   {r['sigma_in']:8.3f}   {r['mse']:13.3f}   {r['psnr']:11.2f} dB   "
+                f"{r['divergence']:10.4f}   {100.0 * r['clipped_fraction']:6.2f}%")
+    for i, r in enumerate(report["batches"]):
+        lines.append(line(str(i), "x".join(map(str, r["shape"])), r))
+    lines.append(line("all", "", report["aggregate"]))
+    return "\n".join(lines)

@@ -638,6 +638,28 @@ int bf_op_dihedral_stack_u8(const uint8_t* src, uint8_t* dst_even, uint8_t* dst_
 int bf_op_dihedral_merge(const float* src_even, const float* src_odd, void* out, int B, int H, int W, int C, int members,
                          int out_u8, void* stream);
 
+/* ---- risk estimation without a clean image: Stein's unbiased risk estimate around a denoiser (blind_image_denoising_amd/risk.py
+ * is the host side; csrc/risk.hip).  For y = x + n, n ~ N(0, sigma^2): E |f(y) - x|^2 / N = E[ |f(y) - y|^2 / N - sigma^2 +
+ * (2 sigma^2 / N) div f(y) ], div f(y) ~ s . (f(y + a s) - f(y)) / a for a random sign vector s (Ramani, Blu, Unser 2008).
+ * Probe p = 1..probes (at most 8) of amplitude a = `amplitude` grey levels (1..16).  Sign of element e = (h W + w) C + c of an
+ * image (the same for every image of a batch): j = e >> 2, i = e & 3, r = philox4x32_10(counter = (lo32 j, hi32 j, p, 2),
+ * key = (lo32 seed, hi32 seed)), s = +1 when bit 31 of r[i] is set, else -1; s = -s when y + a s leaves 0..255.
+ * channels in 1..4, any B, H, W >= 1 with H W C < 2^31 - 4096.  Neither entry allocates or synchronises: graph-capturable.
+ * BF_EINVAL for NULL, a bad shape, `probes` or `amplitude`, or short or misaligned scratch.
+ *
+ * bf_op_risk_probe_u8: dst = uint8 [(1 + probes) B, H, W, C], member-major: member 0 = src, member p = src + a s_p.  src is read
+ *   once; one Philox call serves four elements; one launch.  src must not alias dst.
+ * bf_op_risk_sums: y = the uint8 batch, f = the float32 result for the stack above, [(1 + probes) B, H, W, C];
+ *   out = device double[B][C][1 + probes]:  out[n][c][0] = sum over h, w of (f_0 - y)^2,  out[n][c][p] = sum of s_p (f_p - f_0),
+ *   s_p regenerated from (seed, p, e, y), every term formed in fp64 from the fp32 and uint8 values.  Reduced in a fixed order
+ *   (per-workgroup partials in `scratch`, bf_op_risk_sums_scratch_bytes bytes, 8-byte aligned; then one workgroup per image):
+ *   repeated calls return the same bits, and an image inside a batch the bits of that image alone. */
+int bf_op_risk_probe_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int probes, int amplitude, uint64_t seed,
+                        void* stream);
+int64_t bf_op_risk_sums_scratch_bytes(int B, int H, int W, int C, int probes);
+int bf_op_risk_sums(const uint8_t* y, const float* f, int B, int H, int W, int C, int probes, int amplitude, uint64_t seed,
+                    void* scratch, int64_t scratch_bytes, double* out, void* stream);
+
 /* ---- options and diagnostics (not part of the drop-in surface; used by tests/) ------------- */
 
 /* Inference forwards keep a status word in the LAST 2048 bytes of the workspace they are given (ws + ws_bytes - 2048,
