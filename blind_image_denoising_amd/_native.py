@@ -188,6 +188,7 @@ SIGNATURES = {
     "bf_get_train_kernels": (C.c_char_p, [_P]),
     "bf_debug_conv3x3": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "bf_debug_conv3x3_grid": (_I, [_I, _I, _I]),
+    "bf_debug_h3_weight_scale": (_F, [_F]),
     "bf_debug_fused_block": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "bf_debug_fused_block_h3_scratch_floats": (_I64, [_I, _I, _I]),
     "bf_debug_fused_block_h3": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

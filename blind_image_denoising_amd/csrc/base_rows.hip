@@ -16,6 +16,7 @@
 // Takes u8 input, cin = 3, k = 3, value range [0, 255], split-planar output; everything else stays on the vector kernel.
 #include "bf_common.h"
 #include "h3_core.h"
+#include "h3_weights.h"
 #include <cstdlib>
 
 constexpr int BR_NT = 256, BR_CW = 256, BR_RING = 4, BR_ROWPX = BR_CW + 4;      // ring pixels: image columns x0 - 1 .. x0 + 258
@@ -30,29 +31,12 @@ __global__ __launch_bounds__(BR_NT) void base_conv_rows_kernel(BaseConvArgs a, i
     if (a.status && blockIdx.x == 0 && tid == 0) *a.status = 0;               // first kernel of a forward
     const float* __restrict__ w = a.w;                                         // [3][3][3][16] HWIO
 
-    // ---- A operands: (w / 255 | -0.5 sum_c w) * s split into hi / lo; s = the power of two that puts the largest entry in [2^13, 2^14)
+    // ---- A operands: (w / 255 | -0.5 sum_c w) * s split into hi / lo; s = the weight scale of the largest entry (h3_weights.h)
     auto wval = [&](const int tap, const int c, const int m) -> float {
         if (c < 3) return w[(tap * 3 + c) * 16 + m] / 255.0f;
         return -0.5f * (w[(tap * 3 + 0) * 16 + m] + w[(tap * 3 + 1) * 16 + m] + w[(tap * 3 + 2) * 16 + m]);
     };
-    float mx = 0.f;
-    for (int i = tid; i < 9 * 4 * 16; i += BR_NT) mx = fmaxf(mx, fabsf(wval(i / 64, (i >> 4) & 3, i & 15)));
-    red[tid] = mx;
-    __syncthreads();
-    for (int st = BR_NT / 2; st > 0; st >>= 1) {
-        if (tid < st) red[tid] = fmaxf(red[tid], red[tid + st]);
-        __syncthreads();
-    }
-    float s = 1.f;
-    {
-        const float m0 = red[0];
-        if (m0 > 0.f && m0 < 3.0e38f) {
-            int ex;
-            (void)frexpf(m0, &ex);
-            ex = max(-100, min(100, ex));
-            s = ldexpf(1.f, 14 - ex);
-        }
-    }
+    const float s = bf_h3_block_weight_scale<BR_NT>([&](const int i) { return wval(i / 64, (i >> 4) & 3, i & 15); }, 9 * 4 * 16, red);
     const float inv_s = 1.0f / s;
     h8 wa[3];
 #pragma unroll
@@ -63,8 +47,9 @@ __global__ __launch_bounds__(BR_NT) void base_conv_rows_kernel(BaseConvArgs a, i
             const int slot = 8 * (q & 1) + j, dx = slot >> 2, c = slot & 3;
             float v = 0.f;
             if (dx < 3) v = wval(dy * 3 + dx, c, n) * s;
-            const _Float16 hi = (_Float16)v;
-            wa[dy][j] = (q >> 1) ? (_Float16)(v - (float)hi) : hi;
+            _Float16 hi, lo;
+            bf_h3_split(v, hi, lo);
+            wa[dy][j] = (q >> 1) ? lo : hi;
         }
     }
 

@@ -1,6 +1,7 @@
 // Single-kernel entry points for tests/ and the timing tools (include/bfcnn_hip_debug.h).  They take no handle and need nothing from
 // the engine: each packs its own weights into the caller's scratch buffer and calls one launcher of bf_common.h.
 #include "bf_common.h"
+#include "h3_weights.h"
 #include <cstring>
 
 // ------------------------------------------------------------------------------------------
@@ -270,6 +271,9 @@ extern "C" int bf_debug_wgrad3x3(const float* x, const float* dy, float* partial
 {
     return bf_launch_wgrad3x3_c16(x, dy, partial, dw, B, H, W, (hipStream_t)stream) == hipSuccess ? BF_OK : BF_EHIP;
 }
+
+// the split-f16 weight scale as the kernels evaluate it (h3_weights.h), on the host
+extern "C" float bf_debug_h3_weight_scale(float max_abs) { return bf_h3_weight_scale(max_abs); }
 
 // raw MFMA layout probe: D = A(16x4) * B(4x16) with A[m][k] = a_in[m*4+k], B[k][n] = b_in[k*16+n]
 __global__ void mfma_probe_kernel(const float* a_in, const float* b_in, float* d_out)

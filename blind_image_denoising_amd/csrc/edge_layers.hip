@@ -2,6 +2,7 @@
 // denoiser head + denormalisation + uint8 store.  Both are HBM-bound (64 B/pixel of fp32
 // activations against <2 % of the FLOPs), so they are plain VALU kernels with 16-byte accesses.
 #include "bf_common.h"
+#include "block_reduce.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
@@ -441,22 +442,11 @@ __global__ __launch_bounds__(256) void head_train_kernel(HeadTrainArgs a, int bl
         for (int i = 0; i < 4; ++i) dp[i] = make_float4(df[4 * i], df[4 * i + 1], df[4 * i + 2], df[4 * i + 3]);
     }
     // wave reduction then cross-wave through LDS (fixed order)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int i = 0; i < 64; ++i) {
-        float v = M[i];
+    for (int i = 0; i < 64; ++i) bf_tile_stage(red, i, M[i]);
+    const float sv[4] = {s_abs, s_hinge, s_sq, s_sqh};
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-        if (lane == 0) red[wave][i] = v;
-    }
-    float sv[4] = {s_abs, s_hinge, s_sq, s_sqh};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float v = sv[i];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-        if (lane == 0) red[wave][64 + i] = v;
-    }
+    for (int i = 0; i < 4; ++i) bf_tile_stage(red, 64 + i, sv[i]);
     __syncthreads();
     if (threadIdx.x < 80) {
         const int i = threadIdx.x;

@@ -1,5 +1,6 @@
 // The optimiser of the C-ABI engine.
 #include "engine.h"
+#include "block_reduce.h"
 #include <cmath>
 
 // ------------------------------------------------------------------------------------------
@@ -14,14 +15,9 @@ __global__ __launch_bounds__(1024) void grad_norm_kernel(const float* __restrict
         const double v = (double)g[i] * grad_scale;
         acc += v * v;
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 512; st > 0; st >>= 1) {
-        if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
+    const double sum = bf_block_reduce<1024, BfSum>(red, (int)threadIdx.x, acc);
     if (threadIdx.x == 0) {
-        scratch[0] = (float)sqrt(red[0]);
+        scratch[0] = (float)sqrt(sum);
         if (losses) losses[BF_LOSS_GRAD_NORM] = scratch[0];
     }
 }
@@ -57,13 +53,8 @@ __global__ __launch_bounds__(256) void tensor_clip_factor_kernel(const float* __
         const double x = (double)g[i] * grad_scale;
         acc += x * x;
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) factor[blockIdx.x] = clipnorm / fmaxf((float)sqrt(red[0]), clipnorm);
+    const double sum = bf_block_reduce<256, BfSum>(red, (int)threadIdx.x, acc);
+    if (threadIdx.x == 0) factor[blockIdx.x] = clipnorm / fmaxf((float)sqrt(sum), clipnorm);
 }
 
 __global__ __launch_bounds__(256) void adam_tensor_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

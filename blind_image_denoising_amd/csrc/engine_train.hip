@@ -1,6 +1,7 @@
 // Training half of the C-ABI engine: bf_train_step = train_step_single_gpu (forward in training mode, head + loss, backward,
 // regularisers) as one stream-ordered launch sequence, and the small kernels only the step launches.
 #include "engine.h"
+#include "block_reduce.h"
 #include <cstring>
 #include <cmath>
 
@@ -107,12 +108,7 @@ __global__ __launch_bounds__(1024) void head_finalize_kernel(const float* __rest
         for (; k < blocks_per_image; ++k) sq += (double)partial[(size_t)(b * blocks_per_image + k) * 80 + 66];
         acc += sqrt(sq / per_image + 1e-3);
     }
-    rm[tid] = acc;
-    __syncthreads();
-    for (int st = 512; st > 0; st >>= 1) {
-        if (tid < st) rm[tid] += rm[tid + st];
-        __syncthreads();
-    }
+    const double rm_sum = bf_block_reduce<1024, BfSum>(rm, tid, acc);
     // dW0[c][j] = sum_o M[c][o] * W1[j][o] ; dW1[j][o] = sum_c W0[c][j] * M[c][o]
     for (int i = tid; i < 16 * hf; i += 1024) {
         const int c = i / hf, j = i % hf;
@@ -130,7 +126,7 @@ __global__ __launch_bounds__(1024) void head_finalize_kernel(const float* __rest
         const double mae_actual = sums[0] / numel;
         const double mae_loss = mae_multiplier > 0.f ? sums[1] / numel : 0.0;
         losses[BF_LOSS_MAE] = (float)mae_actual;
-        losses[BF_LOSS_MSE] = (float)(rm[0] / (double)B);
+        losses[BF_LOSS_MSE] = (float)(rm_sum / (double)B);
         losses[BF_LOSS_SSIM] = 0.f;
         losses[BF_LOSS_DENOISER_TOTAL] = (float)(mae_loss * mae_multiplier);
         losses[BF_LOSS_TOTAL] = (float)(mae_loss * mae_multiplier * depth_weight);     // + model loss added by reg kernel
@@ -165,13 +161,8 @@ __global__ __launch_bounds__(1024) void regularizer_kernel(const float* __restri
             grads[i] = grads[i] + regularization * 0.02f * w;
         }
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 512; st > 0; st >>= 1) {
-        if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) wg_sums[blockIdx.x] = red[0];
+    const double sum = bf_block_reduce<1024, BfSum>(red, (int)threadIdx.x, acc);
+    if (threadIdx.x == 0) wg_sums[blockIdx.x] = sum;
 }
 
 __global__ void regularizer_finalize_kernel(const double* __restrict__ wg_sums, float regularization, float* __restrict__ losses)

@@ -16,6 +16,7 @@
 //            and split, ARE the B fragment of K chunk c of the closing 1x1: 6 MFMAs per pixel group.  The 128-channel tensor exists
 //            only as 32 registers.
 #include "unet_h3_core.h"
+#include "h3_weights.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -32,34 +33,14 @@ static_assert(UG_TILE_OFF % 16 == 0 && 2 * UG_LDS_BYTES <= 160 * 1024, "two work
 template <bool RELU>
 __device__ __forceinline__ float ug_act(float v, float slope) { return RELU ? fmaxf(v, 0.f) : fmaxf(v, slope * v); }
 
-// power of two s with max |w| s in [2^13, 2^14): the lo halves of the scaled weights stay normal f16 numbers
-__device__ float ug_block_scale(const float* __restrict__ w, int n, float* red)
-{
-    float m = 0.f;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) m = fmaxf(m, fabsf(w[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int st = blockDim.x / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    const float mx = red[0];
-    __syncthreads();
-    if (!(mx > 0.f) || !isfinite(mx)) return 1.f;
-    int ex;
-    (void)frexpf(mx, &ex);
-    ex = max(-100, min(100, ex));
-    return ldexpf(1.f, 14 - ex);
-}
-
 // packed operand: [W0 fragments 4 KB | W2 fragments 16 KB | depthwise [9][128] fp32 | 1/s0, 1/s2, 0, 0]
 // fragment f = (chunk * 2 + tile) * 2 + (0 hi | 1 lo); element (f * 64 + lane) * 8 + i, lane = 16 q + m: W[32 chunk + 8 q + i][16 tile + m] * s
 __global__ __launch_bounds__(256) void ug_pack_bneck_kernel(const float* __restrict__ w0, const float* __restrict__ wd,
                                                             const float* __restrict__ w2, char* __restrict__ dst)
 {
     __shared__ float red[256];
-    const float s0 = ug_block_scale(w0, 32 * 32, red);
-    const float s2 = ug_block_scale(w2, 128 * 32, red);
+    const float s0 = bf_h3_block_weight_scale<256>([&](const int i) { return w0[i]; }, 32 * 32, red);       // h3_weights.h
+    const float s2 = bf_h3_block_weight_scale<256>([&](const int i) { return w2[i]; }, 128 * 32, red);
     _Float16* d0 = reinterpret_cast<_Float16*>(dst);
     _Float16* d2 = reinterpret_cast<_Float16*>(dst + UG_W0_BYTES);
     for (int e = threadIdx.x; e < UG_W0_BYTES / 2 + UG_W2_BYTES / 2; e += 256) {
@@ -68,8 +49,9 @@ __global__ __launch_bounds__(256) void ug_pack_bneck_kernel(const float* __restr
         const int i = el & 7, lane = (el >> 3) & 63, f = el >> 9;
         const int hl = f & 1, t = (f >> 1) & 1, c = f >> 2, q = lane >> 4, m = lane & 15;
         const float v = second ? w2[(32 * c + 8 * q + i) * 32 + 16 * t + m] * s2 : w0[(8 * q + i) * 32 + 16 * t + m] * s0;
-        const _Float16 hi = (_Float16)v;
-        (second ? d2 : d0)[el] = hl ? (_Float16)(v - (float)hi) : hi;
+        _Float16 hi, lo;
+        bf_h3_split(v, hi, lo);
+        (second ? d2 : d0)[el] = hl ? lo : hi;
     }
     float* dw = reinterpret_cast<float*>(dst + UG_W0_BYTES + UG_W2_BYTES);
     for (int e = threadIdx.x; e < UG_DW_FLOATS; e += 256) dw[e] = wd[e];

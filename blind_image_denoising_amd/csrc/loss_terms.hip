@@ -11,6 +11,7 @@
 // q - a^2 - b^2 cancels five digits, so the window sums are carried in fp64 (the matrix of the work is tiny: 49 taps).
 // dS/dx[p] = sum over the windows w covering p of g[p - w] * (dS/da[w] + y[p] dS/ds[w] + 2 x[p] dS/dq[w]).
 #include "bf_common.h"
+#include "block_reduce.h"
 #include <math.h>
 
 struct SsimWindow { float g[49]; };
@@ -46,8 +47,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
         dS[i] = (float)(grad_scale * lum * 2.0 / dc);
         dQ[i] = (float)(grad_scale * -lum * nc / (dc * dc));
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+    acc = bf_wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = (float)((red[0] + red[1]) + (red[2] + red[3]));
@@ -69,23 +69,11 @@ __global__ __launch_bounds__(256) void loss_extra_prepare_kernel(const float* __
         coef[b] = (float)((double)mse_scale / ((double)B * per_image * rm));
         acc += rm;
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    const double rm_mean = red[0] / (double)B;
-    __syncthreads();
+    const double rm_mean = bf_block_reduce<256, BfSum>(red, (int)threadIdx.x, acc) / (double)B;
     acc = 0.0;
     for (int i = threadIdx.x; i < n_ssim; i += 256) acc += (double)ssim_partial[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { scal[0] = (float)rm_mean; scal[1] = (float)red[0]; }
+    const double ssim_sum = bf_block_reduce<256, BfSum>(red, (int)threadIdx.x, acc);
+    if (threadIdx.x == 0) { scal[0] = (float)rm_mean; scal[1] = (float)ssim_sum; }
 }
 
 // dextra[p] = (ssim part, pre-scaled by -ssim_multiplier * depth_weight / windows) - coef[b] * relu'(gt - pred)

@@ -11,14 +11,16 @@
 //      at most 26 x 104 elements each; the squared / absolute differences of the elements the tile owns ride in this pass;
 //   2. row pass: per staged row and lane the four moments g*x, g*y, g*(x y), g*(x^2 + y^2) over the F horizontal taps -> LDS;
 //   3. column pass: the F vertical taps over those, then S, summed per lane;
-//   4. wave shuffle + LDS reduction in a fixed order -> one partial triple per workgroup in scratch.
-// A second launch (one workgroup per image) adds the partials of an image in a fixed order: two calls on the same input
-// return the same bits; there are no atomics.  All lanes of a wave read consecutive LDS words: no bank conflicts.
+//   4. one partial triple per workgroup in scratch (bf_tile_stage / bf_tile_partials).
+// A second launch (one workgroup per image) adds the partials of an image (bf_finalize_partials).  Both stages are the fixed-order
+// sum of block_reduce.h: two calls on the same input return the same bits; there are no atomics.  All lanes of a
+// wave read consecutive LDS words: no bank conflicts.
 //
 // Numerics.  q - a^2 - b^2 cancels five digits, so the moments and S are carried in fp64 (fp64 FMA is half the fp32 rate on
 // gfx950 and the kernel has 8 F multiply-adds per window: cheap next to any denoiser forward).  uint8 differences are
 // accumulated as integers per thread and as fp64 from there on (integers below 2^53: exact in any order).
 #include "bf_common.h"
+#include "block_reduce.h"
 #include <math.h>
 
 namespace {
@@ -105,34 +107,22 @@ __global__ __launch_bounds__(256) void image_metrics_tile_kernel(const T* __rest
             ssim += (nl / dl) * (nc / dc);
         }
 
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        ssd += __shfl_xor(ssd, m); sad += __shfl_xor(sad, m); ssim += __shfl_xor(ssim, m);
-    }
-    if (lane == 0) { red[wave][0] = ssd; red[wave][1] = sad; red[wave][2] = ssim; }
-    __syncthreads();
-    if (threadIdx.x < 3)
-        partial[(int64_t)blockIdx.x * 3 + threadIdx.x] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    bf_tile_stage(red, 0, ssd);
+    bf_tile_stage(red, 1, sad);
+    bf_tile_stage(red, 2, ssim);
+    bf_tile_partials(red, 3, partial + (int64_t)blockIdx.x * 3);
 }
 
 // out[img] = {sum of squared differences, sum of absolute differences, sum of S, number of S terms}; one workgroup per image
 __global__ __launch_bounds__(256) void image_metrics_finalize_kernel(const double* __restrict__ partial, int64_t tiles, double terms,
                                                                      double* __restrict__ out)
 {
-    __shared__ double red[3][256];
+    __shared__ double red[256];
     const double* p = partial + (int64_t)blockIdx.x * tiles * 3;
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int64_t i = threadIdx.x; i < tiles; i += 256)
-        for (int j = 0; j < 3; ++j) acc[j] += p[i * 3 + j];
-    for (int j = 0; j < 3; ++j) red[j][threadIdx.x] = acc[j];
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st)
-            for (int j = 0; j < 3; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + st];
-        __syncthreads();
+    for (int j = 0; j < 3; ++j) {
+        const double sum = bf_finalize_partials(p + j, tiles, 3, red);
+        if (threadIdx.x == 0) out[(int64_t)blockIdx.x * 4 + j] = sum;
     }
-    if (threadIdx.x < 3) out[(int64_t)blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0];
     if (threadIdx.x == 3) out[(int64_t)blockIdx.x * 4 + 3] = terms;
 }
 

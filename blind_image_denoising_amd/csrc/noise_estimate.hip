@@ -18,9 +18,10 @@
 //
 // Exactness.  uint8: |L| <= 2040 and every count are integers, summed per lane in 32 bits (at most 8 terms) and in 64-bit integers
 // from the wave reduction on: S, the histogram and the clipped count are exact and independent of the order (the atomics add integers).  float32: h, L and the sums are formed in double and
-// reduced in a fixed order (wave shuffle, LDS, per-workgroup partials in scratch, one workgroup per plane): two calls return
-// the same bits, and a plane inside a batch the bits of that plane alone.
+// reduced with the fixed-order two-stage sum of block_reduce.h (one workgroup per plane in the second stage): two
+// calls return the same bits, and a plane inside a batch the bits of that plane alone.
 #include "bf_common.h"
+#include "block_reduce.h"
 #include <math.h>
 #include <type_traits>
 
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(256) void noise_estimate_tile_kernel(const T* __res
     using A = NeAcc<T>;
     using V = typename std::conditional<U8, int, double>::type;      // per lane: at most 8 terms |L| <= 2040
     __shared__ unsigned hist[U8 ? NE_MAXC : 1][NE_BINS_PAD];
-    __shared__ A red[4][NE_MAXC][2];
+    __shared__ A red[4][NE_MAXC * 2];                             // quantity 2 c + {0: S, 1: clipped count}
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int t = blockIdx.x;
     const int tx = t % tiles_x;
@@ -102,16 +103,10 @@ __global__ __launch_bounds__(256) void noise_estimate_tile_kernel(const T* __res
 
 #pragma unroll
     for (int c = 0; c < NE_MAXC; ++c) {
-        A ws = (A)s[c], wc = (A)clip[c];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { ws += __shfl_xor(ws, m); wc += __shfl_xor(wc, m); }
-        if (lane == 0) { red[wave][c][0] = ws; red[wave][c][1] = wc; }
+        bf_tile_stage(red, 2 * c, (A)s[c]);
+        bf_tile_stage(red, 2 * c + 1, (A)clip[c]);
     }
-    __syncthreads();
-    if ((int)threadIdx.x < C * 2) {
-        const int c = threadIdx.x >> 1, j = threadIdx.x & 1;
-        partial[((int64_t)blockIdx.x * C + c) * 2 + j] = (red[0][c][j] + red[1][c][j]) + (red[2][c][j] + red[3][c][j]);
-    }
+    bf_tile_partials(red, C * 2, partial + (int64_t)blockIdx.x * C * 2);
     if constexpr (U8) {
         for (int i = threadIdx.x; i < C * NE_BINS_PAD; i += 256) {
             const int c = i / NE_BINS_PAD, k = i % NE_BINS_PAD;
@@ -128,25 +123,17 @@ __global__ __launch_bounds__(256) void noise_estimate_finalize_kernel(const A* _
                                                                       double* __restrict__ out)
 {
     constexpr bool U8 = std::is_same<A, long long>::value;
-    __shared__ A red[2][256];
+    __shared__ A red[256];
     __shared__ unsigned long long cum[NE_BINS_PAD];
     const int b = blockIdx.x / C, c = blockIdx.x % C, tid = threadIdx.x;
     const A* p = partial + (int64_t)b * tiles * C * 2 + c * 2;
-    A acc[2] = {(A)0, (A)0};
-    for (int64_t i = tid; i < tiles; i += 256)
-        for (int j = 0; j < 2; ++j) acc[j] += p[i * C * 2 + j];
-    for (int j = 0; j < 2; ++j) red[j][tid] = acc[j];
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st)
-            for (int j = 0; j < 2; ++j) red[j][tid] += red[j][tid + st];
-        __syncthreads();
-    }
+    const A sum_s = bf_finalize_partials(p, tiles, (int64_t)C * 2, red);
+    const A sum_clip = bf_finalize_partials(p + 1, tiles, (int64_t)C * 2, red);
     double* o = out + (int64_t)blockIdx.x * 4;
     if (tid == 0) {
-        o[0] = (double)red[0][0];
-        o[1] = fast_scale * (double)red[0][0] / interior;
-        o[3] = U8 ? (double)red[1][0] : (double)NAN;
+        o[0] = (double)sum_s;
+        o[1] = fast_scale * (double)sum_s / interior;
+        o[3] = U8 ? (double)sum_clip : (double)NAN;
         if (!U8) o[2] = (double)NAN;
     }
     if constexpr (U8) {

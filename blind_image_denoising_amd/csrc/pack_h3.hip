@@ -1,13 +1,12 @@
 // Inference weight packs of the split-f16 fused blocks (fused_h3.hip, fused_h3v.hip, fused_h3w.hip read them).
 #include "bf_common.h"
+#include "h3_weights.h"
 
 // ------------------------------------------------------------------------------------------
 // One workgroup per (layer, conv).  dst per block (BF_H3_BLOCK_FLOATS): [aux 64 floats][w1r][w2r] with, per convolution,
-// thirteen A-operand register images [i][lane][8 x f16] in the row-streaming layout:
-//   i = dy*4 + {0: pair (dy,0)|(dy,1) hi, 1: pair lo, 2: single (dy,2) [hi | hi], 3: single [lo | 0]}, i = 12: sr * identity;
-//   lane l: output channel l & 15, k-slots 8*(l >> 4) .. +7 (k-slot < 16: first tap of the pair, >= 16: second tap; input
-//   channel = k-slot & 15).
-// The weights are pre-scaled by a power of two sr (max |w * fold| * sr in [2^13, 2^14)) so that w_lo stays a normal f16 number.
+// thirteen A-operand register images [i][lane][8 x f16] in the row-streaming layout: twelve weight images (bf_h3_row_operand,
+// h3_weights.h) and i = 12: sr * identity.
+// The weights are pre-scaled by the power of two sr of max |w * fold| (the rule of h3_weights.h).
 // conv2 (which == 1): the folded BN scale is multiplied INTO the weights (per output channel) and the kernels add the
 // residual as (sr * I) x [x_hi | x_lo] on the matrix pipe, so sr must itself be an f16 number: sr <= 2^15.
 // aux[0..15] = 1/s1, aux[32..47] = folded BN shift, aux[48..63] = 1/s2 (aux[16..31] is not used).
@@ -21,7 +20,6 @@ __global__ __launch_bounds__(256) void pack_h3_kernel(const float* __restrict__ 
     const int layer = blockIdx.x >> 1, which = blockIdx.x & 1;
     const float* w = params + p_blocks + layer * p_stride + which * 2304;      // HWIO [3][3][16][16]
     __shared__ float s_fold[16];
-    __shared__ float s_scale_r;
     if (threadIdx.x < 16) {
         float f = 1.f;
         if (which == 1) {
@@ -31,45 +29,18 @@ __global__ __launch_bounds__(256) void pack_h3_kernel(const float* __restrict__ 
         s_fold[threadIdx.x] = f;
     }
     __syncthreads();
-    float m = 0.f;
-    for (int i = threadIdx.x; i < 2304; i += 256) m = fmaxf(m, fabsf(w[i] * s_fold[i & 15]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float sr = 1.f;
-        const float mx = red[0];
-        if (mx > 0.f && mx < 3.0e38f) {
-            int ex;
-            (void)frexpf(mx, &ex);                   // mx = f * 2^ex, f in [0.5, 1)
-            ex = max(-100, min(100, ex));
-            sr = ldexpf(1.f, 14 - ex);               // mx * sr in [2^13, 2^14)
-        }
-        if (which == 1) sr = fminf(sr, 32768.f);
-        s_scale_r = sr;
-    }
-    __syncthreads();
-    const float sr = s_scale_r;
+    float sr = bf_h3_block_weight_scale<256>([&](const int i) { return w[i] * s_fold[i & 15]; }, 2304, red);
+    if (which == 1) sr = fminf(sr, 32768.f);         // conv2: sr itself is an f16 operand (sr * I carries the residual)
     _Float16* orow = reinterpret_cast<_Float16*>(dst + layer * d_stride + 64 + which * BF_H3R_WPACK_FLOATS);
     for (int idx = threadIdx.x; idx < 13 * 64 * 8; idx += 256) {
-        const int i = idx >> 9, l = (idx >> 3) & 63, j = idx & 7;
-        const int cout = l & 15, kslot = 8 * (l >> 4) + j, half = kslot >> 4, cin = kslot & 15;
-        if (i == 12) {
+        int tap, part, cin, cout;
+        bf_h3_row_operand(idx, tap, part, cin, cout);
+        if (idx >> 9 == 12) {
             orow[idx] = (which == 1 && cin == cout) ? (_Float16)sr : (_Float16)0.f;
             continue;
         }
-        const int dy = i >> 2, kind = i & 3;
-        int tap, part;
-        if (kind == 0) { tap = dy * 3 + half; part = 0; }
-        else if (kind == 1) { tap = dy * 3 + half; part = 1; }
-        else if (kind == 2) { tap = dy * 3 + 2; part = 0; }                 // [w_hi | w_hi] x [x_hi | x_lo]
-        else { tap = dy * 3 + 2; part = half ? 2 : 1; }                       // [w_lo | 0]    x [x_hi | x_lo]
-        const float ws = w[(tap * 16 + cin) * 16 + cout] * s_fold[cout] * sr;
-        const _Float16 hi = (_Float16)ws;
-        const _Float16 lo = (_Float16)(ws - (float)hi);
+        _Float16 hi, lo;
+        bf_h3_split(w[(tap * 16 + cin) * 16 + cout] * s_fold[cout] * sr, hi, lo);
         orow[idx] = part == 0 ? hi : (part == 1 ? lo : (_Float16)0.f);
     }
     float* aux = dst + layer * d_stride;

@@ -17,17 +17,17 @@
 //   probe: a thread owns one group.
 //   sums:  a thread owns RkUnit<C>::T "units" of lcm(4, C) elements, 256 units apart, so that the channel of each of its elements
 //          is a compile-time constant; it keeps y and f_0 of its units in registers and walks the probes over them.
-// Reduction in a fixed order, as metrics.hip: per thread in ascending element order, wave shuffle, LDS over the four waves, one
-// partial per workgroup and quantity in scratch, then one workgroup per image.  Every term is formed in fp64 from the fp32 and
-// uint8 values.  The grid of an image depends on its shape alone: two calls return the same bits, and an image inside a batch
+// Reduction: the fixed-order two-stage sum of block_reduce.h, per thread in ascending element order, then one
+// workgroup per image.  Every term is formed in fp64 from the fp32 and uint8 values.  The grid of an image depends on its shape alone: two calls return the same bits, and an image inside a batch
 // the bits of that image alone.  There are no atomics.
 #include "bf_common.h"
+#include "block_reduce.h"
 #include "philox.h"
 
 namespace {
 
 constexpr int RK_MAXC = 4, RK_MAXK = 8, RK_MAXA = 16;
-constexpr int RK_THREADS = 256;
+constexpr int RK_THREADS = 256;                          // block_reduce.h's two-stage sum is built for 256
 constexpr int RK_MAXQ = RK_MAXC * (1 + RK_MAXK);          // quantities per image: [C][1 + K]
 
 // four probe signs of group j (bit i set: +1 for element 4 j + i), before the reflection
@@ -124,7 +124,6 @@ __global__ __launch_bounds__(RK_THREADS) void risk_sums_tile_kernel(const uint8_
 {
     using U = RkUnit<C>;
     __shared__ double red[4][RK_MAXQ];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.x / tiles, tile = blockIdx.x % tiles;
     const uint8_t* __restrict__ yb = y + (int64_t)b * n;
 
@@ -175,18 +174,10 @@ __global__ __launch_bounds__(RK_THREADS) void risk_sums_tile_kernel(const uint8_
             }
         }
 #pragma unroll
-        for (int c = 0; c < C; ++c) {
-            double w = acc[c];
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) w += __shfl_xor(w, m);
-            if (lane == 0) red[wave][c * (1 + K) + p] = w;
-        }
+        for (int c = 0; c < C; ++c) bf_tile_stage(red, c * (1 + K) + p, acc[c]);
     }
-    __syncthreads();
     const int Q = C * (1 + K);
-    if ((int)threadIdx.x < Q)
-        partial[(int64_t)blockIdx.x * Q + threadIdx.x] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    bf_tile_partials(red, Q, partial + (int64_t)blockIdx.x * Q);
 }
 
 // out[image][c][q] = the partials of the image's workgroups added in a fixed order; one workgroup per image
@@ -196,16 +187,8 @@ __global__ __launch_bounds__(RK_THREADS) void risk_sums_finalize_kernel(const do
     __shared__ double red[RK_THREADS];
     const double* p = partial + (int64_t)blockIdx.x * tiles * Q;
     for (int q = 0; q < Q; ++q) {
-        double acc = 0.0;
-        for (int i = threadIdx.x; i < tiles; i += RK_THREADS) acc += p[(int64_t)i * Q + q];
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        for (int st = RK_THREADS / 2; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[(int64_t)blockIdx.x * Q + q] = red[0];
-        __syncthreads();
+        const double sum = bf_finalize_partials(p + q, tiles, Q, red);
+        if (threadIdx.x == 0) out[(int64_t)blockIdx.x * Q + q] = sum;
     }
 }
 

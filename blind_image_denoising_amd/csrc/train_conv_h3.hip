@@ -4,6 +4,7 @@
 #include "bf_common.h"
 #include "h3_core.h"
 #include "h3_rows.h"
+#include "h3_weights.h"
 
 // ==========================================================================================================
 // Single 3x3 16->16 convolution on fp32 NHWC tensors with the split-f16 arithmetic and the row-streaming inner loop of
@@ -195,48 +196,20 @@ __global__ __launch_bounds__(256) void pack_h3_train_kernel(const float* __restr
     // blockIdx.x = layer * 2 * nconv + which ; which < nconv: forward pack of convolution `which`, else the data-gradient pack
     // of convolution which - nconv.  Convolution j of a block sits at j * 2304 (+ (j - 1) * 16 behind the gammas: unit = 2320)
     __shared__ float red[256];
-    __shared__ float s_scale;
     const int per = 2 * nconv;
     const int layer = blockIdx.x / per, which = blockIdx.x % per;
     const int cj = which % nconv;
     const float* w = params + p_blocks + layer * p_stride + (cj == 0 ? 0 : 2304 + (int64_t)(cj - 1) * unit);
     const int tf = which / nconv;
-    float m = 0.f;
-    for (int i = threadIdx.x; i < 2304; i += 256) m = fmaxf(m, fabsf(w[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float sr = 1.f;
-        const float mx = red[0];
-        if (mx > 0.f && mx < 3.0e38f) {
-            int ex;
-            (void)frexpf(mx, &ex);
-            ex = max(-100, min(100, ex));
-            sr = ldexpf(1.f, 14 - ex);
-        }
-        s_scale = sr;
-    }
-    __syncthreads();
-    const float sr = s_scale;
+    const float sr = bf_h3_block_weight_scale<256>([&](const int i) { return w[i]; }, 2304, red);
     float* out = dst + ((int64_t)layer * per + which) * d_stride;
     _Float16* orow = reinterpret_cast<_Float16*>(out);
     for (int idx = threadIdx.x; idx < 12 * 64 * 8; idx += 256) {
-        const int i = idx >> 9, l = (idx >> 3) & 63, j = idx & 7;
-        const int cout = l & 15, kslot = 8 * (l >> 4) + j, half = kslot >> 4, cin = kslot & 15;
-        const int dy = i >> 2, kind = i & 3;
-        int tap, part;
-        if (kind == 0) { tap = dy * 3 + half; part = 0; }
-        else if (kind == 1) { tap = dy * 3 + half; part = 1; }
-        else if (kind == 2) { tap = dy * 3 + 2; part = 0; }
-        else { tap = dy * 3 + 2; part = half ? 2 : 1; }
+        int tap, part, cin, cout;
+        bf_h3_row_operand(idx, tap, part, cin, cout);
         const float wv = tf ? w[((8 - tap) * 16 + cout) * 16 + cin] : w[(tap * 16 + cin) * 16 + cout];
-        const float ws = wv * sr;
-        const _Float16 hi = (_Float16)ws;
-        const _Float16 lo = (_Float16)(ws - (float)hi);
+        _Float16 hi, lo;
+        bf_h3_split(wv * sr, hi, lo);
         orow[idx] = part == 0 ? hi : (part == 1 ? lo : (_Float16)0.f);
     }
     for (int idx = 12 * 64 * 8 + threadIdx.x; idx < 13 * 64 * 8; idx += 256) orow[idx] = (_Float16)0.f;     // unused 13th image

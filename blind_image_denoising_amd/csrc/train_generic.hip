@@ -6,6 +6,7 @@
 // Exact fp32 tensors, fp64 statistics, fixed summation order (bitwise reproducible), stream-ordered, no allocation.
 // Written for correctness: these networks' training is a parity row (tests/test_gpu_resnet_generic_train.py), not a benchmark.
 #include "bf_common.h"
+#include "block_reduce.h"
 #include <math.h>
 
 namespace {
@@ -572,10 +573,8 @@ __global__ __launch_bounds__(256) void tg_relu_shift_bwd_kernel(const float* __r
     __shared__ double red[256];
     double s = 0.0;
     for (int c = threadIdx.x; c < C; c += 256) s += (double)dm[c];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st]; __syncthreads(); }
-    if (threadIdx.x == 0) dw0[0] = w0[0] + w1 > 0.f ? (float)red[0] : 0.f;
+    const double sum = bf_block_reduce<256, BfSum>(red, (int)threadIdx.x, s);
+    if (threadIdx.x == 0) dw0[0] = w0[0] + w1 > 0.f ? (float)sum : 0.f;
 }
 
 // the same factor with the layers' default activation "linear": m[c] = w0[c or 0] + w1

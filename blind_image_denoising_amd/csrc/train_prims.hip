@@ -7,6 +7,7 @@
 // atomics).  These kernels are written for correctness and clarity first: training of this network is a parity target
 // (tests/test_gpu_unet_train.py against the torch-autograd oracle), not a benchmarked configuration.
 #include "bf_common.h"
+#include "block_reduce.h"
 #include <math.h>
 
 namespace {
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(256) void tp_layernorm_bwd_kernel(const float* __re
             xv[k] = c < C ? x[p * C + c] : 0.f;
             s1 += xv[k];
         }
-        for (int m = 32; m >= 1; m >>= 1) s1 += __shfl_xor(s1, m);
+        s1 = bf_wave_sum(s1);
         const float mu = s1 / C;
         float s2 = 0.f;
         for (int k = 0; k < per_lane; ++k) {
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256) void tp_layernorm_bwd_kernel(const float* __re
             const float d = c < C ? xv[k] - mu : 0.f;
             s2 += d * d;
         }
-        for (int m = 32; m >= 1; m >>= 1) s2 += __shfl_xor(s2, m);
+        s2 = bf_wave_sum(s2);
         const float inv = rsqrtf(s2 / C + eps);
         float sg = 0.f, sgx = 0.f;
         for (int k = 0; k < per_lane; ++k) {
@@ -167,7 +168,8 @@ __global__ __launch_bounds__(256) void tp_layernorm_bwd_kernel(const float* __re
             sgx += gv[k] * xh;
             acc[k] += d * xh;
         }
-        for (int m = 32; m >= 1; m >>= 1) { sg += __shfl_xor(sg, m); sgx += __shfl_xor(sgx, m); }
+        sg = bf_wave_sum(sg);
+        sgx = bf_wave_sum(sgx);
         const float mg = sg / C, mgx = sgx / C;
         for (int k = 0; k < per_lane; ++k) {
             const int c = lane + 64 * k;
@@ -389,11 +391,7 @@ __global__ __launch_bounds__(256) void tp_loss_sums_kernel(const float* __restri
         const float eh = e > hinge ? fminf(e, cutoff * cutoff) : 0.f;
         s[3] += eh * eh;
     }
-    for (int k = 0; k < 4; ++k) {
-        float v = s[k];
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-    }
+    for (int k = 0; k < 4; ++k) bf_tile_stage(red, k, s[k]);
     __syncthreads();
     if (threadIdx.x < 80) {
         float v = 0.f;
@@ -424,18 +422,11 @@ __global__ __launch_bounds__(256) void tp_loss_finalize_kernel(const float* __re
                                                                float depth_weight, float* __restrict__ losses)
 {
     __shared__ double red[256];
-    __shared__ double sums[2];
+    double sums[2];
     for (int col = 0; col < 2; ++col) {
         double s = 0.0;
         for (int r = threadIdx.x; r < nblk; r += 256) s += (double)partial[(size_t)r * 80 + 64 + col];
-        red[threadIdx.x] = s;
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) {
-            if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) sums[col] = red[0];
-        __syncthreads();
+        sums[col] = bf_block_reduce<256, BfSum>(red, (int)threadIdx.x, s);
     }
     double acc = 0.0;
     for (int b = threadIdx.x; b < B; b += 256) {
@@ -443,16 +434,11 @@ __global__ __launch_bounds__(256) void tp_loss_finalize_kernel(const float* __re
         for (int k = 0; k < blocks_per_image; ++k) sq += (double)partial[(size_t)(b * blocks_per_image + k) * 80 + 66];
         acc += sqrt(sq / per_image + 1e-3);
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
+    const double rm_sum = bf_block_reduce<256, BfSum>(red, (int)threadIdx.x, acc);
     if (threadIdx.x == 0) {
         const double mae_loss = mae_multiplier > 0.f ? sums[1] / numel : 0.0;
         losses[BF_LOSS_MAE] = (float)(sums[0] / numel);
-        losses[BF_LOSS_MSE] = (float)(red[0] / (double)B);
+        losses[BF_LOSS_MSE] = (float)(rm_sum / (double)B);
         losses[BF_LOSS_SSIM] = 0.f;
         losses[BF_LOSS_DENOISER_TOTAL] = (float)(mae_loss * mae_multiplier);
         losses[BF_LOSS_TOTAL] = (float)(mae_loss * mae_multiplier * depth_weight);
@@ -483,18 +469,10 @@ __global__ __launch_bounds__(256) void tp_attention_fwd_kernel(const float* __re
     __shared__ float redv[256];
     float mx = -3.4e38f;
     for (int j = threadIdx.x; j < T; j += 256) mx = fmaxf(mx, sc[j]);
-    redv[threadIdx.x] = mx;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) redv[threadIdx.x] = fmaxf(redv[threadIdx.x], redv[threadIdx.x + st]); __syncthreads(); }
-    mx = redv[0];
-    __syncthreads();
+    mx = bf_block_reduce<256, BfMax>(redv, (int)threadIdx.x, mx);
     float sum = 0.f;
     for (int j = threadIdx.x; j < T; j += 256) { sc[j] = expf(sc[j] - mx); sum += sc[j]; }
-    redv[threadIdx.x] = sum;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) redv[threadIdx.x] += redv[threadIdx.x + st]; __syncthreads(); }
-    const float inv = 1.f / redv[0];
-    __syncthreads();
+    const float inv = 1.f / bf_block_reduce<256, BfSum>(redv, (int)threadIdx.x, sum);
     for (int j = threadIdx.x; j < T; j += 256) {
         const float p = sc[j] * inv;
         if (P) P[((size_t)b * T + i) * T + j] = p;                          // the softmax itself (in front of the dropout scale)
@@ -529,11 +507,7 @@ __global__ __launch_bounds__(256) void tp_attention_bwd_rows_kernel(const float*
         ds[j] = dp;
         part = fmaf(dp, P[((size_t)b * T + i) * T + j], part);
     }
-    redv[threadIdx.x] = part;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) redv[threadIdx.x] += redv[threadIdx.x + st]; __syncthreads(); }
-    const float dot = redv[0];
-    __syncthreads();
+    const float dot = bf_block_reduce<256, BfSum>(redv, (int)threadIdx.x, part);
     for (int j = threadIdx.x; j < T; j += 256) {
         const float s = P[((size_t)b * T + i) * T + j] * (ds[j] - dot);
         ds[j] = s;
@@ -613,10 +587,8 @@ __global__ __launch_bounds__(256) void tp_reg_elementwise_kernel(const float* __
             if (grad) grad[i] += grad_scale * coef * 2.f * x;
         }
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st]; __syncthreads(); }
-    if (threadIdx.x == 0) value[0] = (float)((double)value[0] + (double)coef * red[0]);
+    const double sum = bf_block_reduce<256, BfSum>(red, (int)threadIdx.x, acc);
+    if (threadIdx.x == 0) value[0] = (float)((double)value[0] + (double)coef * sum);
 }
 
 // SoftOrthonormalConstraintRegularizer (regularizers.py:283-338) on a 1x1 kernel W [cin][cout]: G = W^T W [cout][cout],
@@ -657,10 +629,8 @@ __global__ __launch_bounds__(256) void tp_so_apply_kernel(const float* __restric
     }
     double acc = 0.0;
     for (int e = threadIdx.x; e < cout * cout; e += 256) acc += (double)G[e];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) { if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st]; __syncthreads(); }
-    if (threadIdx.x == 0) value[0] = (float)((double)value[0] + red[0]);
+    const double sum = bf_block_reduce<256, BfSum>(red, (int)threadIdx.x, acc);
+    if (threadIdx.x == 0) value[0] = (float)((double)value[0] + sum);
 }
 
 __global__ void tp_flip_hw_kernel(const float* __restrict__ w, float* __restrict__ out, int k, int inner)

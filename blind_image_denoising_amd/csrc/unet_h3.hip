@@ -3,8 +3,8 @@
 // (bfcnn/custom_layers.py:990-1008 conv_2 -> activation -> conv_3 -> ChannelLearnableMultiplier; the Add of
 // backbone_unet_laplacian.py:351-354.)  Same arithmetic as the resnet blocks (fused_h3.hip): every fp32
 // operand v is carried as hi = f16(v), lo = f16(v - hi) (22 mantissa bits), a product is w_hi x_hi + w_lo x_hi + w_hi x_lo
-// on v_mfma_f32_16x16x32_f16 with fp32 accumulation; the weights are pre-scaled by a power of two so that their lo parts
-// stay normal f16 numbers.  3 MFMAs of 16 cycles contract K = 32 where the fp32 path (unet_ops.hip) needs 8 MFMAs of 32
+// on v_mfma_f32_16x16x32_f16 with fp32 accumulation; the weights are pre-scaled by the power of two of
+// h3_weights.h.  3 MFMAs of 16 cycles contract K = 32 where the fp32 path (unet_ops.hip) needs 8 MFMAs of 32
 // cycles: 5.3x fewer matrix-pipe cycles, which makes the kernel HBM-bound (x + skip + out = 12 C bytes per pixel).
 //
 // Data flow per wave and 16 pixels (N = pixel, M = output channel of a tile):
@@ -15,6 +15,7 @@
 //          k(q, i) = 32 c2 + 16 (i / 4) + 4 q + (i % 4); W2 is packed in that order.  The 4C-wide hidden tensor never
 //          exists outside a pair of accumulators.
 #include "unet_h3_core.h"
+#include "h3_weights.h"
 #ifndef UH_NP32
 #define UH_NP32 2                  // 16-pixel groups a wave of the C = 32 MLP kernels carries through the two GEMMs at a time
 #endif
@@ -27,27 +28,8 @@
 // fragment f = (chunk * tiles + tile) * 2 + (0 hi | 1 lo); element (f * 64 + lane) * 8 + i, lane = 16 q + m
 //   W1: value W1[32 chunk + 8 q + i][16 tile + m] * s1
 //   W2: value W2[32 chunk + 16 (i / 4) + 4 q + (i % 4)][16 tile + m] * s2
-// s = power of two with max |w| s in [2^13, 2^14)
+// s = the weight scale of each matrix (h3_weights.h)
 // ------------------------------------------------------------------------------------------
-__device__ float uh_block_scale(const float* __restrict__ w, int n, float* red)
-{
-    float m = 0.f;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) m = fmaxf(m, fabsf(w[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int st = blockDim.x / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    const float mx = red[0];
-    __syncthreads();
-    if (!(mx > 0.f) || !isfinite(mx)) return 1.f;
-    int ex;
-    (void)frexpf(mx, &ex);                                           // mx = f 2^ex, f in [0.5, 1)
-    ex = max(-100, min(100, ex));
-    return ldexpf(1.f, 14 - ex);
-}
-
 // chain = 1 (C = 32): W1 in the K order of W2, k(q, i) = 16 (i / 4) + 4 q + (i % 4) -- the order in which a lane of the OUTPUT layout
 // holds a pixel's 32 channels (tile 0 registers, tile 1 registers), so that a block's output is the next block's B fragment as it stands
 // (uh_chain32_kernel)
@@ -56,8 +38,8 @@ __global__ __launch_bounds__(256) void uh_pack_mlp_kernel(const float* __restric
 {
     __shared__ float red[256];
     const int H = 4 * C;
-    const float s1 = uh_block_scale(w1, C * H, red);
-    const float s2 = uh_block_scale(w2, C * H, red);
+    const float s1 = bf_h3_block_weight_scale<256>([&](const int i) { return w1[i]; }, C * H, red);
+    const float s2 = bf_h3_block_weight_scale<256>([&](const int i) { return w2[i]; }, C * H, red);
     const int n = C * H;                                             // values per matrix; 2 n halves per matrix
     for (int e = threadIdx.x; e < 2 * n; e += 256) {
         const int i = e & 7, lane = (e >> 3) & 63, f = e >> 9;
@@ -66,15 +48,15 @@ __global__ __launch_bounds__(256) void uh_pack_mlp_kernel(const float* __restric
         {
             const int T = H / 16, t = ct % T, c = ct / T;
             const int k1 = chain ? 16 * (i >> 2) + 4 * q + (i & 3) : 32 * c + 8 * q + i;
-            const float v = w1[k1 * H + 16 * t + m] * s1;
-            const _Float16 hi = (_Float16)v;
-            dst[e] = hl ? (_Float16)(v - (float)hi) : hi;
+            _Float16 hi, lo;
+            bf_h3_split(w1[k1 * H + 16 * t + m] * s1, hi, lo);
+            dst[e] = hl ? lo : hi;
         }
         {
             const int T = C / 16, t = ct % T, c = ct / T;
-            const float v = w2[(32 * c + 16 * (i >> 2) + 4 * q + (i & 3)) * C + 16 * t + m] * s2;
-            const _Float16 hi = (_Float16)v;
-            dst[2 * n + e] = hl ? (_Float16)(v - (float)hi) : hi;
+            _Float16 hi, lo;
+            bf_h3_split(w2[(32 * c + 16 * (i >> 2) + 4 * q + (i & 3)) * C + 16 * t + m] * s2, hi, lo);
+            dst[2 * n + e] = hl ? lo : hi;
         }
     }
     if (threadIdx.x == 0) {

@@ -5,6 +5,7 @@
 // contraction takes 3 x 3 MFMAs of 16 cycles per output tile instead of 19 of 32 cycles, which moves the kernel from the
 // fp32 matrix pipe (0.59 ms at 32 x 512 x 512) to the 128 B/px it writes.
 #include "unet_h3_core.h"
+#include "h3_weights.h"
 
 //
 // Round 4: the kernel size is a template parameter (3, 5, 7): the base convolution of the resnet configs is the same operator with
@@ -63,27 +64,12 @@ __global__ __launch_bounds__(256) void uf_first_conv_tile_kernel(const void* __r
             float v = rv[i];
             if (inpad[i] && normalize) v = (fminf(fmaxf(v, v_min), v_max) - v_min) / range - 0.5f;
             if (!inpad[i]) v = 0.f;
-            const _Float16 hi = (_Float16)v;
-            const _Float16 lo = (_Float16)(v - (float)hi);
+            _Float16 hi, lo;
+            bf_h3_split(v, hi, lo);
             if (e < UF_NE) tile[e] = (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
         }
     }
-    // power-of-two scale that puts the largest weight in [2^13, 2^14): the lo parts stay normal f16 numbers
-    float mx = 0.f;
-    for (int i = threadIdx.x; i < UF_KT * UF_COUT; i += 256) mx = fmaxf(mx, fabsf(w[i]));
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    mx = red[0];
-    float scale = 1.f;
-    if (mx > 0.f && isfinite(mx)) {
-        int ex;
-        (void)frexpf(mx, &ex);
-        scale = ldexpf(1.f, 14 - max(-100, min(100, ex)));
-    }
+    const float scale = bf_h3_block_weight_scale<256>([&](const int i) { return w[i]; }, UF_KT * UF_COUT, red);     // h3_weights.h
     const float inv = 1.f / scale;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, n = lane & 15;
     // contraction index k = 32 s + 8 q + i  (tap = k / 3, channel = k % 3; k >= 75: zero weight)
@@ -189,22 +175,7 @@ __global__ __launch_bounds__(256) void uf_first_conv_kernel(const void* __restri
         }
     };
     if ((int)blockIdx.x < ntiles) request(blockIdx.x);
-    // power-of-two scale that puts the largest weight in [2^13, 2^14): the lo parts stay normal f16 numbers
-    float mx = 0.f;
-    for (int i = threadIdx.x; i < UF_KT * UF_COUT; i += 256) mx = fmaxf(mx, fabsf(w[i]));
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    mx = red[0];
-    float scale = 1.f;
-    if (mx > 0.f && isfinite(mx)) {
-        int ex;
-        (void)frexpf(mx, &ex);
-        scale = ldexpf(1.f, 14 - max(-100, min(100, ex)));
-    }
+    const float scale = bf_h3_block_weight_scale<256>([&](const int i) { return w[i]; }, UF_KT * UF_COUT, red);     // h3_weights.h
     const float inv = 1.f / scale;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, n = lane & 15;
     // contraction index k = 32 s + 8 q + i  (tap = k / 3, channel = k % 3; k >= UF_KT: zero weight)
@@ -246,8 +217,8 @@ __global__ __launch_bounds__(256) void uf_first_conv_kernel(const void* __restri
             float v = (inpad && yy < Hs && xx < Ws) ? rv[i] : 0.f;               // the pad band between the source and [H, W] is value 0
             if (inpad && normalize) v = (fminf(fmaxf(v, v_min), v_max) - v_min) / range - 0.5f;
             if (!inpad) v = 0.f;
-            const _Float16 hi = (_Float16)v;
-            const _Float16 lo = (_Float16)(v - (float)hi);
+            _Float16 hi, lo;
+            bf_h3_split(v, hi, lo);
             if (e < UF_NE) tile[e] = (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
         }
         __syncthreads();

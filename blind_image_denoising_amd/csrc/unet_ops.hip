@@ -13,6 +13,7 @@
 //     vector kernels: C/4 lanes per pixel, 16-byte accesses, channel reductions with DPP shuffles inside a wave.
 #include "bf_common.h"
 #include "unet_h3_core.h"
+#include "h3_weights.h"
 #include <math.h>
 
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -1747,7 +1748,7 @@ extern "C" int bf_op_head_fused(const float* in, const float* ln_gamma, float ep
 // cycles (433 us per batch of 32 x 512 x 512 at 32 channels: the fp32 matrix chain and the epilogue's vector work did not overlap).
 // Lane (q, n) loads channels 32c + 8q .. + 7 of pixel n (the B fragment of K chunk c); the weight fragments are built once per wave from
 // the fp32 operand bf_op_pack_pointwise wrote (element W0[16 c16 + 4 q' + j][16 t + m] at ((c16 * 2 + t) * 64 + 16 q' + m) * 4 + j),
-// scaled by a power of two that puts the largest weight in [2^13, 2^14).
+// scaled by the weight scale of the largest one (h3_weights.h).
 // NO = output channels the per-pixel epilogue carries (3 for the colour models: a quarter of its multiplies and one of its four lane sums less than 4)
 template <int CIN, int NO>
 __global__ __launch_bounds__(256, 2) void uo_head_fused_h3_kernel(const float* __restrict__ in, const float* __restrict__ gamma, float eps,
@@ -1758,21 +1759,7 @@ __global__ __launch_bounds__(256, 2) void uo_head_fused_h3_kernel(const float* _
 {
     constexpr int KC = CIN / 32, T = 2, NP = 2;
     __shared__ float red[256];
-    float mx = 0.f;
-    for (int i = threadIdx.x; i < CIN * 32; i += 256) mx = fmaxf(mx, fabsf(w0p[i]));
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
-        __syncthreads();
-    }
-    mx = red[0];
-    float scale = 1.f;
-    if (mx > 0.f && isfinite(mx)) {
-        int ex;
-        (void)frexpf(mx, &ex);
-        scale = ldexpf(1.f, 14 - max(-100, min(100, ex)));
-    }
+    const float scale = bf_h3_block_weight_scale<256>([&](const int i) { return w0p[i]; }, CIN * 32, red);
     const float inv = 1.f / scale;
     const int lane = threadIdx.x & 63, q = lane >> 4, n = lane & 15;
     uh8 wh[KC][T], wlo[KC][T];

@@ -93,6 +93,9 @@ int bf_debug_bwd3x3_h3(const float* x, const float* g, const float* c, const flo
             | "head"                               the launch also runs the head
    in that order; the final " head" stands for the head kernel and is absent exactly when a launch is marked "head". */
 int bf_debug_forward_plan(bf_handle h, int batch, int height, int width, int pad_pow2, char* out, int out_bytes);
+/* the power of two every split-f16 operator scales a weight matrix of maximum magnitude max_abs by (csrc/h3_weights.h): a host
+   call of the function the kernels call */
+float bf_debug_h3_weight_scale(float max_abs);
 int bf_debug_mfma_probe(const float* a, const float* b, float* d, void* stream);
 /* bf_upsample2x on C % 4 != 0 maps: 1 (default) the row-walking 16-byte kernel, 0 the 4-byte row kernel (same bits; A/B and tests) */
 int bf_debug_set_upsample_band(int on);

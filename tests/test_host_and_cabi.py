@@ -49,7 +49,7 @@ def test_ctypes_signatures_match_the_header_prototypes():
     text = _header_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"//[^\n]*", "", text)
-    protos = re.findall(r"\b(?:const\s+char\s*\*|int64_t|int|void|bf_handle)\s*(bf_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
+    protos = re.findall(r"\b(?:const\s+char\s*\*|int64_t|int|void|float|bf_handle)\s*(bf_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
     names = [n for n, _ in protos]
     assert sorted(set(names)) == _declared_symbols(), sorted(set(_declared_symbols()) - set(names))
     scalar = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "uint64_t": C.c_uint64, "unsigned": C.c_uint,
@@ -516,3 +516,28 @@ def test_graphed_module_argument_checks():
     assert g.captured_shapes() == [] and g.name == m.name
     with pytest.raises(ValueError):
         g(np.zeros((1, 8, 8, 3), np.float32))
+
+
+def test_h3_weight_scale_rule():
+    """bf_debug_h3_weight_scale is a host call of the one function every split-f16 operator scales its weights with
+    (csrc/h3_weights.h): s = 2^(14 - clip(exponent of m, -100, 100)) bit for bit, 1 for a zero or non-finite maximum, and
+    m * s in [2^13, 2^14) wherever the clamp is not active."""
+    f = N.lib().bf_debug_h3_weight_scale
+
+    def rule(m):
+        if not (m > 0 and np.isfinite(m)):
+            return np.float32(1.0)
+        return np.float32(np.ldexp(1.0, 14 - int(np.clip(np.frexp(m)[1], -100, 100))))
+
+    f32 = np.float32
+    edges = [f32(0.0), f32(-0.0), np.finfo(f32).tiny, f32(2.0 ** -120), f32(0.125), np.nextafter(f32(0.125), f32(0.0)), f32(1.0),
+             f32(3.0), f32(2.0 ** 110), np.finfo(f32).max, f32(np.inf), f32(np.nan)]
+    sweep = np.exp2(np.random.default_rng(20).uniform(-126.0, 127.99, 1000)).astype(f32)
+    assert np.isfinite(sweep).all() and (sweep >= np.finfo(f32).tiny).all()
+    for m in edges + list(sweep):
+        got = f32(f(float(m)))
+        assert got.tobytes() == rule(m).tobytes(), (m, got, rule(m))
+        if m > 0 and np.isfinite(m) and -100 <= np.frexp(m)[1] <= 100:
+            assert 2.0 ** 13 <= float(m) * float(got) < 2.0 ** 14, (m, got)
+    for m in (0.0, np.inf, np.nan):
+        assert f(m) == 1.0
