@@ -35,6 +35,8 @@ from .metrics import ImageMetrics, image_metrics, image_metric_sums, psnr, ssim,
 from .noise_estimate import NoiseEstimate, noise_statistics, noise_summary, estimate_noise, evaluate_blind
 from . import risk
 from .risk import RiskEstimate, risk_probe_stack_u8, risk_sums, estimate_risk, evaluate_blind_risk, format_risk_report
+from . import neighbor
+from .neighbor import neighbor_pairs, NeighborPairs, RiskValidator, parse_self_supervised_config
 from . import regularizers
 from . import pruning
 from .pruning import (PruneStrategy, prune_function_builder, get_conv2d_weights, conv2d_sparsity, conv2d_ranges)

@@ -337,19 +337,22 @@ class DataParallelTrainer:
 # ---- outer loop --------------------------------------------------------------------------------
 
 def train_loop(pipeline_config_path, checkpoint_directory: str = None, weights_dir: str = None, dataset: Iterable = None,
-               device=None, max_steps: Optional[int] = None, model_dir: str = None, evaluation_batches: Iterable = None):
+               device=None, max_steps: Optional[int] = None, model_dir: str = None, evaluation_batches: Iterable = None,
+               validation_noisy_batches: Iterable = None):
     """bfcnn/train_loop.py:40-601 with the reference's positional order (pipeline_config_path, checkpoint_directory, weights_dir);
     `model_dir` is this package's older keyword for the same directory.  Returns (model, loss history).  `evaluation_batches`:
-    clean uint8 batches for the `train.evaluation` section instead of its `inputs` directories.  See `_train_loop`."""
+    clean uint8 batches for the `train.evaluation` section instead of its `inputs` directories; `validation_noisy_batches`: noisy
+    uint8 batches for `train.self_supervised.validation` instead of its `inputs` directories.  See `_train_loop`."""
     model_dir = checkpoint_directory if checkpoint_directory is not None else model_dir
     if model_dir is None:
         raise ValueError("checkpoint_directory must be given")
     return _train_loop(pipeline_config_path, str(model_dir), dataset, None if weights_dir is None else str(weights_dir), device, max_steps,
-                       evaluation_batches)
+                       evaluation_batches, validation_noisy_batches)
 
 
 def _train_loop(pipeline_config_path, model_dir: str, dataset: Iterable = None, weights_dir: str = None,
-                device=None, max_steps: Optional[int] = None, evaluation_batches: Iterable = None):
+                device=None, max_steps: Optional[int] = None, evaluation_batches: Iterable = None,
+                validation_noisy_batches: Iterable = None):
     """Outer loop of bfcnn/train_loop.py:40-601 reduced to what surrounds the hot path: config ->
     loss / optimizer / model builders -> checkpoint manager (restore the latest checkpoint of `model_dir` if there is one:
     weights, BN statistics, Adam slots, step, epoch -- train_loop.py:158-181) -> epochs over `dataset` (an iterable
@@ -359,6 +362,10 @@ def _train_loop(pipeline_config_path, model_dir: str, dataset: Iterable = None, 
     With a `train.evaluation` section (metrics.parse_evaluation_config) the current weights are validated as the reference's loop
     does when it writes summaries (train_loop.py:507-530), with numbers instead of images: every `every` optimizer steps, or at the
     end of each epoch, one record of metrics.evaluate goes to <model_dir>/evaluation.jsonl and to `model.evaluation_history`.
+    With a `train.self_supervised` section (neighbor.parse_self_supervised_config; {"type": "neighbor2neighbor", "gamma", "ramp"}) the
+    dataset is wrapped in neighbor.NeighborPairs: only its noisy half is read, and every step trains g1(y) towards g2(y) of a noisy
+    batch y (Neighbor2Neighbor; no clean image is needed).  Its optional `validation` part appends one record of
+    risk.evaluate_blind_risk (SURE) on fixed noisy batches to <model_dir>/risk.jsonl and to `model.risk_history`, at the same points.
     The tf.data pipeline, TensorBoard summaries and TF's checkpoint format are out of scope."""
     from .checkpoint import Checkpoint, CheckpointManager
     config = load_config(pipeline_config_path)
@@ -392,6 +399,14 @@ def _train_loop(pipeline_config_path, model_dir: str, dataset: Iterable = None, 
     from .metrics import build_evaluator
     evaluator = build_evaluator(train_config, model, model_dir, config.get(DATASET_STR), evaluation_batches)
     model.evaluation_history = evaluator.history if evaluator is not None else []
+    from .neighbor import NeighborPairs, build_risk_validator, parse_self_supervised_config
+    self_supervised = parse_self_supervised_config(train_config)
+    validator = build_risk_validator(self_supervised, model, model_dir, config.get(DATASET_STR), validation_noisy_batches)
+    model.risk_history = validator.history if validator is not None else []
+    pairs = None
+    if self_supervised is not None:
+        pairs = dataset = NeighborPairs(dataset, model=model, gamma=self_supervised.gamma, ramp=self_supervised.ramp,
+                                        seed=train_config.get("seed"))
     # per-output loss weights over the course of training (bfcnn/train_loop.py:350-381, optimizer.py:21-78)
     no_outputs = int(getattr(model, "depth", 1)) if getattr(model, "multi_output", False) else 1
     deep_supervision_schedule = deep_supervision_schedule_builder(
@@ -410,6 +425,8 @@ def _train_loop(pipeline_config_path, model_dir: str, dataset: Iterable = None, 
         else:
             percentage_done = 0.0
         depth_weight = tuple(float(v) for v in deep_supervision_schedule(percentage_done=percentage_done))
+        if pairs is not None:
+            pairs.percentage_done = percentage_done
         logger.info("percentage done [{:.2f}], weight per output index: {}".format(percentage_done, ["{0:.2f}".format(d) for d in depth_weight]))
         for input_image_batch, noisy_image_batch in dataset:
             total, _, denoiser_loss, _, grads = fns.train_step_single_gpu(input_image_batch, noisy_image_batch, depth_weight,
@@ -427,12 +444,16 @@ def _train_loop(pipeline_config_path, model_dir: str, dataset: Iterable = None, 
                 ckpt.step += 1
                 if evaluator is not None and evaluator.due(ckpt.step):
                     evaluator.run(ckpt.step, ckpt.epoch)
+                if validator is not None and validator.due(ckpt.step):
+                    validator.run(ckpt.step, ckpt.epoch)
                 if (0 < total_steps <= ckpt.step) or (max_steps is not None and len(history) >= max_steps):
                     finished = True
                     break
         logger.info(f"end of epoch [{ckpt.epoch}], step {ckpt.step}, took [{time.time() - t0:.1f}] seconds")
         if evaluator is not None and evaluator.config.every <= 0:
             evaluator.run(ckpt.step, ckpt.epoch)
+        if validator is not None and validator.config.every <= 0:
+            validator.run(ckpt.step, ckpt.epoch)
         save_model(model, os.path.join(model_dir, f"epoch_{ckpt.epoch}"), config)
         if not finished:
             ckpt.epoch += 1

@@ -660,6 +660,25 @@ int64_t bf_op_risk_sums_scratch_bytes(int B, int H, int W, int C, int probes);
 int bf_op_risk_sums(const uint8_t* y, const float* f, int B, int H, int W, int C, int probes, int amplitude, uint64_t seed,
                     void* scratch, int64_t scratch_bytes, double* out, void* stream);
 
+/* ---- training on noisy images alone: Neighbor2Neighbor pairs (Huang et al., CVPR 2021; blind_image_denoising_amd/neighbor.py is
+ * the host side; csrc/neighbor.hip).  From a noisy batch y [B,H,W,C] (uint8 when y_is_u8 != 0, else float32; H, W even and >= 2,
+ * C in 1..4) the sampler picks, in every 2x2 cell, an ordered pair of adjacent pixels: input = g1(y), target = g2(y), both float32
+ * [B,H/2,W/2,C].  With f = the denoiser's float32 output for y [B,H,W,C] (NULL: none) the paper's regulariser is folded into the
+ * target, target = g2(y) + lambda (g1(f) - g2(f)), lambda = gamma / (1 + gamma) in [0, 1): for a squared loss
+ * |p - g2|^2 + gamma |p - g2 - d|^2 = (1 + gamma) |p - (g2 + lambda d)|^2 + const.
+ * Cell and group: W2 = W / 2; cell (i, j) of image b belongs to Philox group g = i ceil(W2 / 4) + (j >> 2) (never across a row).
+ * Draw: r = philox4x32_10(counter = (lo32 g, hi32 g, b, 3), key = (lo32 seed, hi32 seed)), k = r[j & 3] >> 29.
+ * Positions of a cell: 0 = (0,0), 1 = (0,1), 2 = (1,0), 3 = (1,1) (row, column); (p1, p2) = T[k],
+ * T = [(0,1),(0,2),(1,3),(2,3),(1,0),(2,0),(3,1),(3,2)], the eight ordered 4-adjacent pairs.  One k for all channels of a cell;
+ * the images of a batch draw differently (b is in the counter).
+ * Outputs: input = (float) y[p1]; target = (float) y[p2] when f is NULL, else fmaf(lambda, f[p1] - f[p2], (float) y[p2]) with the
+ * difference rounded to fp32 first.  y and f are read once, each output is written once.  A float y with f = NULL and lambda = 0
+ * samples any tensor (f(y) itself, for instance) with the same pairs.
+ * One launch, no allocation, no synchronisation: graph-capturable.  BF_EINVAL for NULL y / input / target, B < 1, odd or zero H or W,
+ * C outside 1..4, a lambda that is not finite or outside [0, 1), or an output that overlaps y, f or the other output. */
+int bf_op_neighbor_pairs(const void* y, int y_is_u8, const float* f, float lambda, float* input, float* target, int B, int H, int W,
+                         int C, uint64_t seed, void* stream);
+
 /* ---- options and diagnostics (not part of the drop-in surface; used by tests/) ------------- */
 
 /* Inference forwards keep a status word in the LAST 2048 bytes of the workspace they are given (ws + ws_bytes - 2048,
