@@ -212,6 +212,7 @@ SIGNATURES = {
     "bf_debug_bwd3x3_h3_grid_ex": (_I, [_I, _I, _I, _I]),
     "bf_debug_bwd3x3_h3": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bf_debug_forward_plan": (_I, [_P, _I, _I, _I, _I, C.c_char_p, _I]),
+    "bf_debug_base_path": (_I, [_P, _I, _I, _I, _I, _I]),
     "bf_debug_mfma_probe": (_I, [_P, _P, _P, _P]),
 }
 

@@ -14,9 +14,7 @@
 //   * a workgroup walks down a band of rows of a 256-column chunk: the [r, g, b, 1] f16 records of four input rows live in an LDS
 //     ring (8 bytes per pixel), row y+2 is requested from global memory while row y is multiplied; ONE barrier per row.
 // Takes u8 input, cin = 3, k = 3, value range [0, 255], split-planar output; everything else stays on the vector kernel.
-#include "bf_common.h"
-#include "h3_core.h"
-#include "h3_weights.h"
+#include "base_rows.h"
 #include <cstdlib>
 
 constexpr int BR_NT = 256, BR_CW = 256, BR_RING = 4, BR_ROWPX = BR_CW + 4;      // ring pixels: image columns x0 - 1 .. x0 + 258
@@ -31,27 +29,12 @@ __global__ __launch_bounds__(BR_NT) void base_conv_rows_kernel(BaseConvArgs a, i
     if (a.status && blockIdx.x == 0 && tid == 0) *a.status = 0;               // first kernel of a forward
     const float* __restrict__ w = a.w;                                         // [3][3][3][16] HWIO
 
-    // ---- A operands: (w / 255 | -0.5 sum_c w) * s split into hi / lo; s = the weight scale of the largest entry (h3_weights.h)
-    auto wval = [&](const int tap, const int c, const int m) -> float {
-        if (c < 3) return w[(tap * 3 + c) * 16 + m] / 255.0f;
-        return -0.5f * (w[(tap * 3 + 0) * 16 + m] + w[(tap * 3 + 1) * 16 + m] + w[(tap * 3 + 2) * 16 + m]);
-    };
-    const float s = bf_h3_block_weight_scale<BR_NT>([&](const int i) { return wval(i / 64, (i >> 4) & 3, i & 15); }, 9 * 4 * 16, red);
+    // ---- A operands: (w / 255 | -0.5 sum_c w) * s split into hi / lo; s = the weight scale of the largest entry (base_rows.h)
+    const float s = br_weight_scale(w, red);
     const float inv_s = 1.0f / s;
     h8 wa[3];
 #pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            // k-slot 8 (q & 1) + j of the half (q >> 1): slots 0..3 = tap dx 0, 4..7 = dx 1, 8..11 = dx 2, 12..15 = unused
-            const int slot = 8 * (q & 1) + j, dx = slot >> 2, c = slot & 3;
-            float v = 0.f;
-            if (dx < 3) v = wval(dy * 3 + dx, c, n) * s;
-            _Float16 hi, lo;
-            bf_h3_split(v, hi, lo);
-            wa[dy][j] = (q >> 1) ? lo : hi;
-        }
-    }
+    for (int dy = 0; dy < 3; ++dy) wa[dy] = br_operand(w, s, dy, lane);
 
     int bx = blockIdx.x;
     const int ch = bx % nchunks; bx /= nchunks;

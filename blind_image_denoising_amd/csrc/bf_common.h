@@ -213,6 +213,12 @@ struct FusedH3WArgs {
     int head_u8, Ho, Wo, denormalize;
     float v_min, v_max;
     int* status;           // |= BF_STATUS_F16_RANGE when a block output is not finite; may be NULL
+    // first launch of a forward with the base convolution inside it (base_u8 != NULL; bf_base_conv_rows_supports holds, the launch
+    // is neither reversed nor carries the head): x0 = [relu](conv3x3(normalise(base_u8))) is produced row by row in LDS, bit for
+    // bit what base_conv_rows_kernel writes; `in` is not read and `status` is cleared (first kernel of the forward)
+    const void* base_u8;   // uint8 [B,Hs,Ws,3]; H x W is the (virtually) padded frame
+    const float* base_w;   // [3][3][3][16] HWIO
+    int Hs, Ws, base_relu;
 };
 hipError_t bf_launch_fused_block2_h3w(const FusedH3WArgs& a, hipStream_t s);
 bool       bf_fused_block2_h3w_supports(int H, int W);
@@ -336,6 +342,7 @@ struct BaseConvArgs {
     int* status;          // inference: forward status word, zeroed here (first kernel of a forward); may be NULL
 };
 hipError_t bf_launch_base_conv(const BaseConvArgs& a, hipStream_t s);
+bool       bf_base_conv_runs_rows(const BaseConvArgs& a);              // bf_launch_base_conv would launch base_conv_rows_kernel
 bool       bf_base_conv_rows_supports(const BaseConvArgs& a);          // base_rows.hip: u8, 3x3x3 -> 16, [0, 255], split-planar out
 hipError_t bf_launch_base_conv_rows(const BaseConvArgs& a, hipStream_t s);
 void       bf_set_base_conv_rows(int on);     // 1 (default): the row-streaming matrix-core kernel where it applies; 0: vector kernel (A/B)

@@ -133,10 +133,15 @@ static bool base_rows_preferred(const BaseConvArgs& a)
     return (int64_t)a.B * a.H * nchunks >= 8192 && (int64_t)a.W * 5 >= nchunks * 256 * 3;
 }
 
+bool bf_base_conv_runs_rows(const BaseConvArgs& a)
+{
+    return g_base_rows && bf_base_conv_rows_supports(a) && (g_base_rows == 2 || base_rows_preferred(a));
+}
+
 hipError_t bf_launch_base_conv(const BaseConvArgs& a, hipStream_t s)
 {
     // the metric's configuration (u8 in, 3x3x3 -> 16, split-planar out): row-streaming matrix-core kernel (base_rows.hip)
-    if (g_base_rows && bf_base_conv_rows_supports(a) && (g_base_rows == 2 || base_rows_preferred(a))) return bf_launch_base_conv_rows(a, s);
+    if (bf_base_conv_runs_rows(a)) return bf_launch_base_conv_rows(a, s);
 #define BF_BASE(C, KK) if (a.cin == C && a.k == KK) return launch_base<C, KK>(a, s);
     BF_BASE(3, 3) BF_BASE(3, 5) BF_BASE(3, 7) BF_BASE(3, 1)
     BF_BASE(1, 3) BF_BASE(1, 5) BF_BASE(1, 7) BF_BASE(1, 1)

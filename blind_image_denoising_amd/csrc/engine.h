@@ -55,6 +55,9 @@ struct bf_engine {
     int h3_pair_head = 0;           // 1: the last pair launch also runs a linear 3-channel head (no head kernel, the last activation is
                                     // never written).  Off by default: measured equal (4.437 vs 4.435 ms per batch of 128): the ~250
                                     // vector instructions per 64 pixels cost the issue-bound launch what the head kernel's pass costs
+    int h3_pair_base = 1;           // 1: where the first launch of a forward is a pair and base_conv_rows_kernel could run, that launch
+                                    // computes the base convolution itself (fused_h3w.hip H3WMem<4>): no base kernel, x0 is never
+                                    // written or read back; the same bits.  0: the base kernel launches (A/B)
     int block_launches = 0;         // launches of the last forward's residual blocks (bf_get_timing)
     const char* block_kernel = "";  // name of the kernel that ran most of them
     std::string train_kernels;      // the block kernels of the last bf_train_step (bf_get_train_kernels)

@@ -289,7 +289,47 @@ struct ForwardRun {
     int* status;
     void* out;
     int out_is_u8;
+    const BaseConvArgs* base;   // not NULL: the first step (a pair) computes the base convolution itself
 };
+
+// The three ways a forward runs its base convolution (bf_debug_base_path reports them by these numbers).
+enum BasePath { BaseVector = 0, BaseRows = 1, BaseInPair = 2 };
+
+// Inside the first launch when that launch is a pair that neither carries the head nor walks last to first, and
+// base_conv_rows_kernel is the kernel that would run (the launch computes that kernel's bits, not the vector kernel's: where the
+// selection prefers the vector kernel a forward keeps its bits too); else whichever kernel bf_launch_base_conv picks.
+static BasePath base_path(bf_handle h, const ForwardPlan& p, const BaseConvArgs& ba)
+{
+    if (!bf_base_conv_runs_rows(ba)) return BaseVector;
+    if (h->h3_pair_base && p.N > 0) {
+        const ForwardStep st = p.next(0, 0);
+        if (st.kind == StepKind::Pair && !st.head && !st.reverse) return BaseInPair;
+    }
+    return BaseRows;
+}
+
+static BaseConvArgs base_conv_args(bf_handle h, const ForwardPlan& p, int B, int Hs, int Ws, int H, int W, int in_is_u8)
+{
+    const bf_resnet_desc& d = h->d;
+    BaseConvArgs ba;
+    ba.in = nullptr; ba.out = nullptr; ba.w = nullptr;
+    ba.B = B; ba.Hs = Hs; ba.Ws = Ws; ba.H = H; ba.W = W; ba.cin = d.in_channels; ba.k = d.kernel_size;
+    ba.in_is_u8 = in_is_u8; ba.act_relu = d.base_activation == BF_ACT_RELU;
+    ba.v_min = d.v_min; ba.v_max = d.v_max;
+    // split-f16 blocks keep the activations split-planar between base conv and head (same bytes as fp32)
+    ba.out_split = p.split;
+    ba.status = nullptr;
+    return ba;
+}
+
+extern "C" int bf_debug_base_path(bf_handle h, int B, int H, int W, int pad_pow2, int in_is_u8)
+{
+    if (!h) return BF_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0) return fail(h, BF_EINVAL, "batch/height/width must be positive (got %d,%d,%d)", B, H, W);
+    const int Hp = pad_pow2 ? pow2_target(H) : H, Wp = pad_pow2 ? pow2_target(W) : W;
+    const ForwardPlan p = make_forward_plan(h, B, Hp, Wp);
+    return base_path(h, p, base_conv_args(h, p, B, H, W, Hp, Wp, in_is_u8 != 0));
+}
 
 static int run_pair(ForwardRun& r, const ForwardStep& st)
 {
@@ -308,6 +348,10 @@ static int run_pair(ForwardRun& r, const ForwardStep& st)
     if (st.head) {                                           // last pair: the linear head rides in its store step
         fa.head_wh = r.pk + h->k_wh; fa.head_out = r.out; fa.head_u8 = r.out_is_u8; fa.Ho = r.Hs; fa.Wo = r.Ws;
         fa.denormalize = d.denormalize; fa.v_min = d.v_min; fa.v_max = d.v_max; fa.status = r.status;
+    }
+    if (r.base && st.first == 0) {                           // first launch: x0 is computed in it, from the images
+        fa.in = nullptr; fa.base_u8 = r.base->in; fa.base_w = r.base->w; fa.Hs = r.base->Hs; fa.Ws = r.base->Ws;
+        fa.base_relu = r.base->act_relu; fa.status = r.status;
     }
     BF_HIP(bf_launch_fused_block2_h3w(fa, r.s), "fused_block2_h3w");
     r.cur ^= 1;
@@ -431,15 +475,11 @@ static int run_forward(bf_handle h, const float* pk, const void* in, int in_is_u
     r.status = (int*)((char*)ws + (ws_bytes - BF_STATUS_BYTES) / 4 * 4);
     r.out = out; r.out_is_u8 = out_is_u8;
 
-    BaseConvArgs ba;
+    BaseConvArgs ba = base_conv_args(h, p, B, Hs, Ws, H, W, in_is_u8);
     ba.in = in; ba.out = r.buf[0]; ba.w = pk + h->k_base;
-    ba.B = B; ba.Hs = Hs; ba.Ws = Ws; ba.H = H; ba.W = W; ba.cin = d.in_channels; ba.k = d.kernel_size;
-    ba.in_is_u8 = in_is_u8; ba.act_relu = d.base_activation == BF_ACT_RELU;
-    ba.v_min = d.v_min; ba.v_max = d.v_max;
-    // split-f16 blocks keep the activations split-planar between base conv and head (same bytes as fp32)
-    ba.out_split = p.split;
     ba.status = r.status;
-    BF_HIP(bf_launch_base_conv(ba, s), "base_conv");
+    r.base = base_path(h, p, ba) == BaseInPair ? &ba : nullptr;
+    if (!r.base) BF_HIP(bf_launch_base_conv(ba, s), "base_conv");
 
     if (h->timing) BF_HIP(h->timed.begin(s), "hipEventRecord");
     for (int i = 0, launch = 0; i < p.N;) {

@@ -29,9 +29,13 @@
 //     second intermediate row s-9; B2 consumes it in step s+1 and completes output row s-11 in step s; stored in s+1.
 //     ONE barrier per step, nrows + 12 steps per band;
 //   * rows and columns outside the image are forced to zero in every ring (they are the NEXT convolution's zero padding,
-//     not values computed from padded input).
+//     not values computed from padded input);
+//   * the FIRST launch of a forward on uint8 images (FusedH3WArgs::base_u8, template parameter BASE) has no loader: it computes
+//     its x0 rows itself, the base convolution of base_rows.hip bit for bit, from uint8 rows (H3WProducer below) -- no base
+//     kernel, and x0 is neither written to nor read from global memory.
 #include "h3v_core.h"
 #include "h3_bands.h"
+#include "base_rows.h"
 
 // wave priorities (s_setprio) per role; H3W_PRIO_SET picks a preset for A/B builds: 1 = younger roles higher (0,1,2,3),
 // 2 = older roles higher (3,2,1,0), 3 = second convolutions high (0,2,0,2), 4 = first convolutions high (2,0,2,0)
@@ -72,6 +76,12 @@
 #define H3W_PRIO_B2 1
 #endif
 
+// unit order: 1 = XCD-contiguous (h3_bands.h): the two strips of an image run on ONE XCD and the 16 columns both read come out of
+// its L2 (FETCH per launch 571 -> 538 MB for 537 MB algorithmic; the same-box A/B within its noise); 0 = launch order (A/B)
+#ifndef H3W_XCD_ORDER
+#define H3W_XCD_ORDER 1
+#endif
+
 struct H3WGeom {
     static constexpr int NG = 9, GW = 16 * NG;         // grid: nine 16-column groups
     static constexpr int G = 3;                        // groups per matrix wave
@@ -86,6 +96,13 @@ struct H3WGeom {
     static constexpr int OUT_PLANE = GW * 16, OUT_SLOT = 4 * OUT_PLANE;       // staging rows are indexed by GRID column too
     static constexpr int X0_OFF = 0, M1_OFF = X0_OFF + 4 * X0_PLANE, X1_OFF = M1_OFF + 4 * M_PLANE, M2_OFF = X1_OFF + 4 * X1_PLANE;
     static constexpr int OUT_OFF = M2_OFF + 4 * M_PLANE, LDS_BYTES = OUT_OFF + NRO * OUT_SLOT;
+    // producer launch only (H3WProducer, behind the rings): the [r, g, b, 1_inside] records of four input rows, each row twice
+    // (the second copy shifted by one pixel, as in base_rows.hip), the base convolution's A operands + 1 / s, reduction scratch
+    static constexpr int BIN_RING = 4, BIN_ROWPX = GW + 4;       // ring pixel j = image column G0 - 1 + j; j <= GW + 1 are written
+    static constexpr int BIN_SLOT = 2 * BIN_ROWPX * 8;
+    static constexpr int BIN_OFF = LDS_BYTES, BWA_OFF = BIN_OFF + BIN_RING * BIN_SLOT, BINVS_OFF = BWA_OFF + 3 * 64 * 16;
+    static constexpr int BRED_OFF = BINVS_OFF + 16, LDS_BYTES_BASE = BRED_OFF + NT * 4;
+    static_assert(LDS_BYTES_BASE <= 160 * 1024 && BIN_OFF % 16 == 0 && BIN_SLOT % 16 == 0 && LDS_BYTES_BASE % 16 == 0, "LDS (producer)");
     static constexpr int LEAD = 12;                    // steps from the first x0 row of a band to the store of its first output row
     static constexpr int NSTAMP = 4;
     static_assert(UNROLL % NRM == 0 && UNROLL % NRO == 0 && UNROLL % NRX1 == 0 && UNROLL % 3 == 0, "static slots");
@@ -102,7 +119,7 @@ struct H3WTile : BandUnit {      // a band of one strip (h3_bands.h) + the strip
 
 __device__ __forceinline__ H3WTile h3w_tile(const FusedH3WArgs& a, const int t)
 {
-    H3WTile r{bf_band_unit<false>(a, t)};
+    H3WTile r{bf_band_unit<H3W_XCD_ORDER != 0>(a, t)};
     r.X0 = r.sx * H3WGeom::SW;
     r.X1 = min(a.W, r.X0 + H3WGeom::SW);
     r.G0 = min(max(r.X0 - 8, 0), max(a.W - H3WGeom::GW, 0));
@@ -561,7 +578,172 @@ struct H3WMem<3> {
     __device__ __forceinline__ void finish() {}
 };
 
-template <bool HEAD>
+// ---------------------------------------------------------------------------------------------------------------------
+// The producer (first launch of a forward, FusedH3WArgs::base_u8; such a launch has no loader and issues no DMA at all): the x0
+// ring rows are computed in the launch from uint8 image rows, with base_conv_rows_kernel's arithmetic (base_rows.h: the same A
+// operands, three dependent MFMAs per 16 pixels in the order dy = 0, 1, 2, the same scale and split), so the ring holds bit for
+// bit what the loader would have fetched.  H3WProducer<NGW, FETCH> is the share of one wave: NGW of the nine 16-pixel groups of a
+// row, and (FETCH) one pixel per lane of the next input row; which roles carry what: H3W_BASE_SPREAD.
+//   * input ring: input row u of a band is image row ybase + u - 5, kept in slot u mod 4.  x0 ring row r (image row ybase + r - 4)
+//     multiplies input rows r, r + 1, r + 2;
+//   * step s: the pixel requested in step s-1 (ring pixel 64 k + lane of fetching wave k, three byte loads) goes to input row
+//     s + 4, the pixel of input row s + 5 is requested, x0 ring row s + 1 is produced from input rows s + 1 .. s + 3: complete at the
+//     barrier that ends step s, one step before A1 reads it (the loader's rows land one step earlier still);
+//   * per band: fill() writes input rows 0 .. 3 and requests row 4, and behind a barrier of its own prologue() produces x0 row 0;
+//   * everything sits in front of the role's step, where no fragment is live; rows / columns outside the image are forced to zero
+//     through the epilogue scale, rows no role reads (r >= nrows + 8) are not produced.
+// Only the top-down walk exists (the first launch of a forward is never reversed).
+// ---------------------------------------------------------------------------------------------------------------------
+#ifndef H3W_BASE_SPREAD
+#define H3W_BASE_SPREAD 1        // 0 = the A2 waves produce three groups each; 1 = one group per wave of B1, A2, B2; 2 = of A1, B1, A2
+#endif
+// groups per wave of a role / the first group of its wave rw / the role whose waves fetch the pixels (never A1: it stores)
+constexpr int h3w_base_groups(const int role)
+{
+    return H3W_BASE_SPREAD == 0 ? (role == 2 ? 3 : 0) : (H3W_BASE_SPREAD == 1 ? (role >= 1 ? 1 : 0) : (role <= 2 ? 1 : 0));
+}
+constexpr int h3w_base_first_group(const int role, const int rw)
+{
+    return H3W_BASE_SPREAD == 0 ? 3 * rw : (H3W_BASE_SPREAD == 1 ? 3 * (role - 1) + rw : 3 * role + rw);
+}
+constexpr bool h3w_base_fetches(const int role) { return role == 2; }
+
+template <int NGW, bool FETCH>
+struct H3WProducer {
+    using Gm = H3WGeom;
+    const FusedH3WArgs& a;
+    char* tx0;
+    char* tring;
+    const char* twa;
+    int g0, fw;                  // first group of the wave; index of the wave among the fetching ones
+    float inv_s, floor_;
+    int wr;                      // lane's LDS byte offset of its 8-byte hi record in x0 ring slot 0, group g0 (as H3WRoleA::wr)
+    int fo;                      // lane's byte offset of its group-g0 B fragment inside an input ring slot
+    int col0;                    // image column of the lane's x0 column in group g0
+    int px, xcol;                // ring pixel this lane fetches (>= GW + 2: none) and its image column
+    const uint8_t* img;
+    unsigned raw[3];             // the pixel requested in the previous step
+    BrPixel rawp;
+    int dslot;                   // (s + 1) mod 5
+
+    __device__ __forceinline__ H3WProducer(const FusedH3WArgs& a_, char* lds, const int g0_, const int fw_)
+        : a(a_), tx0(lds + Gm::X0_OFF), tring(lds + Gm::BIN_OFF), twa(lds + Gm::BWA_OFF), g0(g0_), fw(fw_), wr(0), fo(0), col0(0),
+          px(0), xcol(0), img(nullptr), raw{0u, 0u, 0u}, rawp{false, false}, dslot(0)
+    {
+        inv_s = *reinterpret_cast<const float*>(lds + Gm::BINVS_OFF);
+        floor_ = a.base_relu ? 0.f : -__builtin_inff();
+    }
+    __device__ __forceinline__ void set_tile(const H3WTile& t, const int lane)
+    {
+        const int n = lane & 15, q = lane >> 4, gc0 = 16 * g0 + n;
+        wr = (q >> 1) * Gm::X0_PLANE + (gc0 + 1) * 16 + (q & 1) * 8;
+        // B fragment of lane (n, q): the pixel pair starting at ring pixel p = grid column + 2 (q & 1) (q even: taps dx 0, 1; q odd:
+        // tap dx 2 and a pixel that meets zero weights), from copy p & 1 at its aligned position; group g: + 128 g bytes
+        const int p = gc0 + 2 * (q & 1);
+        fo = ((p & 1) * Gm::BIN_ROWPX + (p & ~1)) * 8;
+        twa = tx0 - Gm::X0_OFF + Gm::BWA_OFF + lane * 16;
+        col0 = t.G0 + gc0;
+        px = 64 * fw + lane;
+        xcol = t.G0 - 1 + px;
+        img = reinterpret_cast<const uint8_t*>(a.base_u8) + (size_t)t.b * a.Hs * a.Ws * 3;
+    }
+    // input row u: this lane's pixel -> raw (plain loads: the compiler waits for them where commit() reads them)
+    __device__ __forceinline__ void request(const H3WTile& t, const int u)
+    {
+        const int yy = t.ybase + u - 5;
+        const bool need = (px < Gm::GW + 2) & (u <= t.nrows + 9);          // rows past x0 row nrows + 7 feed nothing
+        rawp = br_pixel(yy, xcol, a.H, a.W, a.Hs, a.Ws);
+        rawp.inside &= need;
+        rawp.colour &= need;
+        if (rawp.colour) {
+            const uint8_t* p = img + ((size_t)yy * a.Ws + xcol) * 3;
+            raw[0] = p[0];
+            raw[1] = p[1];
+            raw[2] = p[2];
+        }
+    }
+    // raw -> input ring row u: ring pixel j goes to copy 0 at j and to copy 1 at j - 1
+    __device__ __forceinline__ void commit(const int u)
+    {
+        if (px >= Gm::GW + 2) return;
+        const h4 v = br_record(rawp, raw[0], raw[1], raw[2]);
+        h4* row = reinterpret_cast<h4*>(tring + (u & (Gm::BIN_RING - 1)) * Gm::BIN_SLOT);
+        row[px] = v;
+        if (px > 0) row[Gm::BIN_ROWPX + px - 1] = v;
+    }
+    // the wave's groups of x0 ring row r into ring slot `slot`
+    __device__ __forceinline__ void produce(const H3WTile& t, const int r, const int slot)
+    {
+        if (r >= t.nrows + 8) return;                                        // wave-uniform
+        const int y = t.y(r - 4);
+        const bool rowok = (y >= 0) & (y < a.H);
+        f32x4 acc[NGW];
+#pragma unroll
+        for (int g = 0; g < NGW; ++g) acc[g] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            const h8 wa = *reinterpret_cast<const h8*>(twa + dy * 64 * 16);           // re-read every step: not held across the role's step
+            const char* row = tring + ((r + dy) & (Gm::BIN_RING - 1)) * Gm::BIN_SLOT + fo;
+#pragma unroll
+            for (int g = 0; g < NGW; ++g) acc[g] = MFMA_H(wa, *reinterpret_cast<const h8*>(row + g * 128), acc[g]);
+        }
+#pragma unroll
+        for (int g = 0; g < NGW; ++g) {
+            H3VEpi<true> e;
+            e.v = bf_acc_ready(acc[g]);
+            e.sc = (rowok & (col0 + 16 * g < a.W)) ? inv_s : 0.f;            // outside the image: conv1a's zero padding
+            e.floor_ = floor_;
+            e.p = tx0 + wr + slot * Gm::PITCH + g * 256;
+            e.lo_off = 2 * Gm::X0_PLANE;
+            e.all();
+        }
+    }
+    __device__ __forceinline__ void fill(const H3WTile& t)
+    {
+        if constexpr (FETCH) {
+#pragma unroll
+            for (int u = 0; u < Gm::BIN_RING; ++u) {
+                request(t, u);
+                commit(u);
+            }
+            request(t, Gm::BIN_RING);
+        }
+    }
+    __device__ __forceinline__ void prologue(const H3WTile& t)
+    {
+        produce(t, 0, 0);
+        dslot = 1;
+    }
+    __device__ __forceinline__ void begin(const H3WTile& t, const int s)
+    {
+        if constexpr (FETCH) {
+            commit(s + 4);
+            request(t, s + 5);
+        }
+        produce(t, s + 1, dslot);
+        dslot = h3v_wrap(dslot + 1, Gm::NRX0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+};
+
+template <>
+struct H3WProducer<0, false> {     // a wave without a share, and every wave of a launch that fetches its x0 rows
+    __device__ __forceinline__ H3WProducer(const FusedH3WArgs&, char*, int, int) {}
+    __device__ __forceinline__ void set_tile(const H3WTile&, int) {}
+    __device__ __forceinline__ void fill(const H3WTile&) {}
+    __device__ __forceinline__ void prologue(const H3WTile&) {}
+    __device__ __forceinline__ void begin(const H3WTile&, int) {}
+};
+
+// the hook of a role: the head storer replaces the storer in a HEAD launch; a BASE launch has no loader
+template <bool HEAD, bool BASE>
+constexpr int h3w_hook_kind(const int role)
+{
+    const int k = h3w_mem_kind(role);
+    return (HEAD && k == 2) ? 3 : ((BASE && k == 1) ? 0 : k);
+}
+
+template <bool HEAD, bool BASE>
 __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH3WArgs a)
 {
     using Gm = H3WGeom;
@@ -579,8 +761,22 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
     const int gc0 = 16 * Gm::G * rw + n;                        // lane's grid column in its wave's group 0
 
     // ring columns 0 and 145 are the zero padding at an image edge: cleared once, never written
-    for (int i = tid * 16; i < Gm::LDS_BYTES; i += Gm::NT * 16) *reinterpret_cast<f32x4*>(h3w_lds + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // (a BASE launch: so is everything of the input ring that is never written, the pixel past the last pair among it)
+    if (BASE && a.status && blockIdx.x == 0 && tid == 0) *a.status = 0;       // first kernel of a forward
+    for (int i = tid * 16; i < (BASE ? Gm::LDS_BYTES_BASE : Gm::LDS_BYTES); i += Gm::NT * 16)
+        *reinterpret_cast<f32x4*>(h3w_lds + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
     __syncthreads();
+    if constexpr (BASE) {
+        // the base convolution's A operands, as base_conv_rows_kernel computes them in its prologue
+        const float bs = br_weight_scale(a.base_w, reinterpret_cast<float*>(h3w_lds + Gm::BRED_OFF));
+        if (wave == 0) {
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)
+                *reinterpret_cast<h8*>(h3w_lds + Gm::BWA_OFF + (dy * 64 + lane) * 16) = br_operand(a.base_w, bs, dy, lane);
+            if (lane == 0) *reinterpret_cast<float*>(h3w_lds + Gm::BINVS_OFF) = 1.0f / bs;
+        }
+        __syncthreads();
+    }
 
 #if H3V_ABLATE & 32
     unsigned long long stamp_sum[Gm::NSTAMP] = {0, 0, 0, 0}, stamp_prev, real0;
@@ -588,27 +784,34 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
 #endif
 
 #define H3W_ROW_IN_IMAGE(k) ((t.y(k) >= 0) & (t.y(k) < a.H))
-// one band of one strip: R = the matrix role object, M = its memory hook, ACTIVE(s) = the role has a row in step s,
+// one band of one strip: R = the matrix role object, M = its memory hook, P = its share of the producer, ACTIVE(s) = the role has a row in step s,
 // STEP(PH) = the role's step call.  Every role runs the same number of barriers.
-#define H3W_BAND(R, M, ACTIVE, STEP)                                                                          \
+#define H3W_BAND(R, M, P, ACTIVE, STEP)                                                                         \
     for (int ti = blockIdx.x; ti < a.ntiles; ti += gridDim.x) {                                               \
         const H3WTile t = h3w_tile(a, ti);                                                                    \
         R.set_tile(t, a.W, gc0);                                                                              \
         M.set_tile(t, lane);                                                                                  \
+        P.set_tile(t, lane);                                                                                  \
+        if constexpr (BASE) {                                /* producer launch: the first input rows */      \
+            P.fill(t);                                                                                        \
+            h3v_barrier();                                                                                    \
+        }                                                                                                     \
+        P.prologue(t);                                                                                        \
         M.prologue(t);                                                                                        \
-        h3v_barrier();                                       /* x0 row 0 has landed */                        \
+        h3v_barrier();                                       /* x0 row 0 has landed / is complete */          \
         const int nsteps = t.nrows + Gm::LEAD;                                                                \
         int slot5 = 0;                                       /* s mod 5 */                                    \
         for (int s0 = 0; s0 < nsteps; s0 += Gm::UNROLL) {                                                     \
-            H3W_ONE(0, M, ACTIVE, STEP); H3W_ONE(1, M, ACTIVE, STEP); H3W_ONE(2, M, ACTIVE, STEP);            \
-            H3W_ONE(3, M, ACTIVE, STEP); H3W_ONE(4, M, ACTIVE, STEP); H3W_ONE(5, M, ACTIVE, STEP);            \
+            H3W_ONE(0, M, P, ACTIVE, STEP); H3W_ONE(1, M, P, ACTIVE, STEP); H3W_ONE(2, M, P, ACTIVE, STEP);   \
+            H3W_ONE(3, M, P, ACTIVE, STEP); H3W_ONE(4, M, P, ACTIVE, STEP); H3W_ONE(5, M, P, ACTIVE, STEP);   \
         }                                                                                                     \
         M.finish();                                                                                           \
         h3v_barrier();                                                                                        \
     }
-#define H3W_ONE(PH, M, ACTIVE, STEP)                                                                          \
+#define H3W_ONE(PH, M, P, ACTIVE, STEP)                                                                         \
     do {                                                                                                      \
         const int s = s0 + PH;                                                                                \
+        P.begin(t, s);                                                                                        \
         M.begin(t, s, PH);                                                                                    \
         if (ACTIVE(s)) { STEP(PH); }                                                                          \
         else M.after_first_group();                                                                           \
@@ -627,11 +830,12 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         R.tin = tx0; R.tmid = tm1;
         R.init(a.w1r[0], a, a.aux[0], lane, gc0);
         R.skip_last = (H3V_ABLATE & 256) && rw == Gm::NR - 1;
-        H3WMem<(HEAD && h3w_mem_kind(0) == 2) ? 3 : h3w_mem_kind(0)> M(a, tx0, tout, rw, plane_g);
+        H3WMem<h3w_hook_kind<HEAD, BASE>(0)> M(a, tx0, tout, rw, plane_g);
+        H3WProducer<BASE ? h3w_base_groups(0) : 0, BASE && h3w_base_groups(0) && h3w_base_fetches(0)> P(a, h3w_lds, h3w_base_first_group(0, rw), rw);
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));               // weight / scale loads
 #define H3W_ACTIVE(s) ((s) < t.nrows + 8)
 #define H3W_STEP(PH) R.template step<PH>(slot5 * Gm::PITCH, (s >= 2) & H3W_ROW_IN_IMAGE(s - 5), M)
-        H3W_BAND(R, M, H3W_ACTIVE, H3W_STEP)
+        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP)
 #undef H3W_ACTIVE
 #undef H3W_STEP
     } else if (role == 1) {
@@ -641,11 +845,12 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         R.tmid = tm1; R.tres = tx0; R.tout = tx1;
         R.init(a.w2r[0], a, a.aux[0], lane, gc0, true);
         R.skip_last = (H3V_ABLATE & 256) && rw == Gm::NR - 1;
-        H3WMem<(HEAD && h3w_mem_kind(1) == 2) ? 3 : h3w_mem_kind(1)> M(a, tx0, tout, rw, plane_g);
+        H3WMem<h3w_hook_kind<HEAD, BASE>(1)> M(a, tx0, tout, rw, plane_g);
+        H3WProducer<BASE ? h3w_base_groups(1) : 0, BASE && h3w_base_groups(1) && h3w_base_fetches(1)> P(a, h3w_lds, h3w_base_first_group(1, rw), rw);
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));
 #define H3W_ACTIVE(s) (((s) >= 3) & ((s) < t.nrows + 9))
 #define H3W_STEP(PH) R.template step<PH>(h3v_wrap(slot5 + Gm::NRX0 - 1, Gm::NRX0) * Gm::PITCH, (PH % Gm::NRX1) * Gm::PITCH, H3W_ROW_IN_IMAGE(s - 7), M)
-        H3W_BAND(R, M, H3W_ACTIVE, H3W_STEP)
+        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP)
 #undef H3W_ACTIVE
 #undef H3W_STEP
     } else if (role == 2) {
@@ -655,11 +860,12 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         R.tin = tx1; R.tmid = tm2;
         R.init(a.w1r[1], a, a.aux[1], lane, gc0);
         R.skip_last = (H3V_ABLATE & 256) && rw == Gm::NR - 1;
-        H3WMem<(HEAD && h3w_mem_kind(2) == 2) ? 3 : h3w_mem_kind(2)> M(a, tx0, tout, rw, plane_g);
+        H3WMem<h3w_hook_kind<HEAD, BASE>(2)> M(a, tx0, tout, rw, plane_g);
+        H3WProducer<BASE ? h3w_base_groups(2) : 0, BASE && h3w_base_groups(2) && h3w_base_fetches(2)> P(a, h3w_lds, h3w_base_first_group(2, rw), rw);
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));
 #define H3W_ACTIVE(s) (((s) >= 6) & ((s) < t.nrows + 10))
 #define H3W_STEP(PH) R.template step<PH>(((PH + 2) % Gm::NRX1) * Gm::PITCH, H3W_ROW_IN_IMAGE(s - 9), M)
-        H3W_BAND(R, M, H3W_ACTIVE, H3W_STEP)
+        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP)
 #undef H3W_ACTIVE
 #undef H3W_STEP
     } else {
@@ -669,11 +875,12 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         R.tmid = tm2; R.tres = tx1; R.tout = tout;
         R.init(a.w2r[1], a, a.aux[1], lane, gc0, false);
         R.skip_last = (H3V_ABLATE & 256) && rw == Gm::NR - 1;
-        H3WMem<(HEAD && h3w_mem_kind(3) == 2) ? 3 : h3w_mem_kind(3)> M(a, tx0, tout, rw, plane_g);
+        H3WMem<h3w_hook_kind<HEAD, BASE>(3)> M(a, tx0, tout, rw, plane_g);
+        H3WProducer<BASE ? h3w_base_groups(3) : 0, BASE && h3w_base_groups(3) && h3w_base_fetches(3)> P(a, h3w_lds, h3w_base_first_group(3, rw), rw);
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));
 #define H3W_ACTIVE(s) (((s) >= 9) & ((s) < t.nrows + 11))
 #define H3W_STEP(PH) R.template step<PH>(((PH + 1) % Gm::NRX1) * Gm::PITCH, (PH % Gm::NRO) * Gm::OUT_SLOT, true, M)
-        H3W_BAND(R, M, H3W_ACTIVE, H3W_STEP)
+        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP)
 #undef H3W_ACTIVE
 #undef H3W_STEP
     }
@@ -698,7 +905,9 @@ hipError_t bf_launch_fused_block2_h3w(const FusedH3WArgs& args, hipStream_t s)
 {
     using Gm = H3WGeom;
     FusedH3WArgs a = args;
-    if (!a.zeros || !a.in || (!a.out && !a.head_wh) || !bf_fused_block2_h3w_supports(a.H, a.W)) return hipErrorInvalidValue;
+    if (!a.zeros || (!a.in && !a.base_u8) || (!a.out && !a.head_wh) || !bf_fused_block2_h3w_supports(a.H, a.W)) return hipErrorInvalidValue;
+    // the producer launch: the top-down walk only, never with the head, the image inside the frame
+    if (a.base_u8 && (!a.base_w || a.head_wh || a.reverse_tiles || a.Hs < 1 || a.Ws < 1 || a.Hs > a.H || a.Ws > a.W)) return hipErrorInvalidValue;
     if ((int64_t)a.H * a.W * 64 >= ((int64_t)1 << 32)) return hipErrorInvalidValue;      // 32-bit in-image offsets
     const BandPlan p = bf_band_plan(a.B, a.H, (a.W + Gm::SW - 1) / Gm::SW, Gm::LEAD + 2);
     a.nstrips = p.nstrips;
@@ -706,9 +915,11 @@ hipError_t bf_launch_fused_block2_h3w(const FusedH3WArgs& args, hipStream_t s)
     a.tiles_y = p.tiles_y;
     a.ntiles = p.ntiles;
     if (a.head_wh && (!a.head_out || a.Ho < 1 || a.Wo < 1 || a.Ho > a.H || a.Wo > a.W)) return hipErrorInvalidValue;
-    void (*kernel)(FusedH3WArgs) = a.head_wh ? fused_block2_h3w_kernel<true> : fused_block2_h3w_kernel<false>;
-    const hipError_t e = bf_set_max_lds(reinterpret_cast<const void*>(kernel), Gm::LDS_BYTES);      // once per device
+    void (*kernel)(FusedH3WArgs) = a.base_u8 ? fused_block2_h3w_kernel<false, true>
+                                   : a.head_wh ? fused_block2_h3w_kernel<true, false> : fused_block2_h3w_kernel<false, false>;
+    const int lds = a.base_u8 ? Gm::LDS_BYTES_BASE : Gm::LDS_BYTES;
+    const hipError_t e = bf_set_max_lds(reinterpret_cast<const void*>(kernel), lds);      // once per device
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(Gm::NT), Gm::LDS_BYTES, s, a);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(Gm::NT), lds, s, a);
     return hipGetLastError();
 }

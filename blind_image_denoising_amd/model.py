@@ -325,6 +325,15 @@ class HydraModel:
         N.check(n if n < 0 else 0, self._h, "bf_debug_forward_plan")
         return buf.value.decode(), int(n)
 
+    BASE_PATHS = ("base_conv_kernel", "base_conv_rows_kernel", "fused_block2_h3w_kernel")
+
+    def base_path(self, batch: int, height: int, width: int, pad_pow2: bool = True, in_is_u8: bool = True) -> str:
+        """the kernel that would run the base convolution of a forward of this shape with the options as they are: the vector
+        kernel, the row-streaming kernel, or the first two-block launch itself (bf_debug_base_path).  Needs no GPU."""
+        n = self._lib.bf_debug_base_path(self._h, int(batch), int(height), int(width), int(bool(pad_pow2)), int(bool(in_is_u8)))
+        N.check(n if n < 0 else 0, self._h, "bf_debug_base_path")
+        return self.BASE_PATHS[n]
+
     # ---- execution -----------------------------------------------------------------------
     def _as_device(self, x, dtype):
         was_numpy = isinstance(x, np.ndarray)

@@ -704,7 +704,10 @@ int bf_op_neighbor_pairs(const void* y, int y_is_u8, const float* f, float lambd
  * "h3_pair": 1 (default): wherever the full-row streaming kernel applies, consecutive residual blocks run TWO per launch
  *   (fused_block2_h3w_kernel: the activation between them stays in LDS; an odd block count runs its single block first); 0: one
  *   block per launch.  "h3_pair_head": 1: the last pair launch also runs a linear 3-channel head in its store step (no head
- *   kernel); 0 (default; the two measure the same).  "h3_pair" = 2 and "base_rows" = 2 (A/B and tests only) run the two-block kernel /
+ *   kernel); 0 (default; the two measure the same).  "h3_pair_base": 1 (default): where the FIRST launch of a forward is such a pair
+ *   (not reversed, not carrying the head) and the row-streaming base kernel is the one that would run (uint8 RGB, 3x3, [0, 255]; see
+ *   "base_rows"), that launch computes the base convolution itself, bit for bit what the base kernel writes: no base kernel, its
+ *   output is neither written nor read back; 0: the base kernel launches (A/B).  "h3_pair" = 2 and "base_rows" = 2 (A/B and tests only) run the two-block kernel /
  *   the row-streaming base convolution wherever they CAN run instead of where the selection prefers them ("base_rows" = 0: the
  *   tile kernel of the base convolution everywhere; process-wide).
  * "h3_variant": kernel of the split-f16 fused blocks (A/B only; negative = default): 4 full-row streaming where it applies,

@@ -93,6 +93,11 @@ int bf_debug_bwd3x3_h3(const float* x, const float* g, const float* c, const flo
             | "head"                               the launch also runs the head
    in that order; the final " head" stands for the head kernel and is absent exactly when a launch is marked "head". */
 int bf_debug_forward_plan(bf_handle h, int batch, int height, int width, int pad_pow2, char* out, int out_bytes);
+/* Which way a forward of that shape would run its base convolution on this handle, with its options as they are now (pad_pow2 as
+   above; in_is_u8 = 1: bf_forward_u8 / bf_forward_u8_f32, 0: bf_forward_f32): 0 = the vector kernel (base_conv_kernel), 1 = the
+   row-streaming matrix-core kernel (base_conv_rows_kernel), 2 = inside the first two-block launch, which then makes the forward's
+   first kernel (option "h3_pair_base"; only where 1 would be the answer without it).  Host arithmetic only, from the plan the forward runs; a negative BF_E* on bad arguments. */
+int bf_debug_base_path(bf_handle h, int batch, int height, int width, int pad_pow2, int in_is_u8);
 /* the power of two every split-f16 operator scales a weight matrix of maximum magnitude max_abs by (csrc/h3_weights.h): a host
    call of the function the kernels call */
 float bf_debug_h3_weight_scale(float max_abs);
