@@ -2,10 +2,10 @@
 Training of the plain U-Net backbone (`UnetHydra`, bfcnn/backbone_unet.py:18-268): bfcnn/train_loop.py:259-312 -- training-mode
 forward (BatchNormalization on batch statistics, moving statistics updated), denoiser loss, the builder's regularisers and the
 gradient of the total for every trainable tensor -- as an explicit forward / backward walk over the operator library, with the
-parameter / state / gradient views and the steps of GenericResnetTrainGraph (BatchNorm, multipliers, gate, closing layers,
-head and loss, regularisers).  What the unet adds to the resnet
-walk: the entry convolutions, MaxPooling2D (bf_op_maxpool2_bwd: the gradient goes to each window's first maximum in row-major
-order, as TF and torch do), the nearest upsampling (bf_op_upsample2x_bwd) and the concat.  The training forward materialises the
+parameter / state / gradient views and the shared steps of train_graph.TrainGraph (k x k convolution, base, head and loss,
+regulariser loop) and those of GenericResnetTrainGraph (BatchNorm, multipliers, gate, closing layers).  What the unet adds to the
+resnet walk: the entry convolutions, MaxPooling2D (Ops.maxpool2_bwd: the gradient goes to each window's first maximum in row-major
+order, as TF and torch do), the nearest upsampling (Ops.upsample2x_bwd) and the concat.  The training forward materialises the
 concat (the entry's kernel gradient reads it); its data gradient is one convolution C -> 2C with the flipped, transposed kernel,
 sliced into the upsampled half and the skip half.  A skip's gradient is the sum of the decoder's and the pooling's.
 
@@ -20,6 +20,7 @@ from . import _native as N
 from . import unet_laplacian as UL
 from ._native import call
 from .resnet_generic_train import GenericResnetTrainGraph
+from .train_graph import push
 from .unet_backbone import UnetHydra, upsample_concat
 
 
@@ -33,45 +34,20 @@ class UnetBackboneTrainGraph(GenericResnetTrainGraph):
             if UL._act(a)[0] == 3:
                 raise NotImplementedError("unet training: GELU activations are outside the built graph")
 
-    def regularizer(self, name: str, kind: str):
+    def kernel_regularizer(self, name: str):
         """backbone_unet.py:108-125 (kernel_regularizer on every backbone convolution), backbone_blocks.py:146-160 (l2 on the gate),
-        the denoiser's on the head, the multipliers' own L1 (backbone_unet.py:152-164)"""
-        if kind == "bn_gamma":
-            return None
-        if kind in ("channelwise", "multiplier"):
-            return kind
+        the denoiser's on the head"""
         if name.startswith("head/"):
             return self.m.config["denoiser"].get("kernel_regularizer", "l2")
-        if "/gate/" in name:
-            return "l2"
-        return self.m.kernel_regularizer
+        return "l2" if "/gate/" in name else self.m.kernel_regularizer
 
     def conv(self, name: str, x: torch.Tensor, act: str, bn=None):
         """k x k convolution (+ BatchNorm on batch statistics) + activation: (y, backward dy -> dx)"""
-        ops = self.ops
-        w = self.W(name)
-        kk, _, cin, cf = w.shape
         if bn is None:
-            y = UL.conv2d(x, UL.pack_conv(w.contiguous()), cf, kk, 1, act)
-            b_act = lambda dy: ops.act_bwd(y, dy, act)
-        else:
-            y, b_act = self.bn_step(bn, UL.conv2d(x, UL.pack_conv(w.contiguous()), cf, kk, 1, "linear"), act)
-
-        def bwd(dy):
-            g = b_act(dy)
-            Bc, Hc, Wc, _ = x.shape
-            sp, sn = ops._s()
-            call("bf_op_conv2d_wgrad", N.ptr(x), 0, N.ptr(g), N.ptr(self.G(name)), Bc, Hc, Wc, cin, cf, kk, 0, 0.0, 0.0, sp, sn,
-                 N.stream_ptr(g))
-            # data gradient = convolution with the taps flipped and every tap transposed
-            wf = torch.empty_like(w)
-            call("bf_op_flip_hw", N.ptr(w), N.ptr(wf), kk, cin * cf, N.stream_ptr(w))
-            wt = torch.empty((kk, kk, cf, cin), **self.f32)
-            for t_ in range(kk * kk):
-                call("bf_op_transpose2d", N.ptr(wf.view(kk * kk, cin, cf)[t_]), N.ptr(wt.view(kk * kk, cf, cin)[t_]), cin, cf,
-                     N.stream_ptr(wf))
-            return UL.conv2d(g, UL.pack_conv(wt), cin, kk, 1, "linear")
-        return y, bwd
+            return self.conv_step(name, x, act)
+        c, b_conv = self.conv_step(name, x, "linear")
+        y, b_bn = self.bn_step(bn, c, act)
+        return y, lambda dy: b_conv(b_bn(dy))
 
     def blocks(self, f: torch.Tensor, pre: str, drop_scale):
         """resnet_blocks_full (backbone_blocks.py:163-246): (output, backward)"""
@@ -81,15 +57,12 @@ class UnetBackboneTrainGraph(GenericResnetTrainGraph):
             b = f"{pre}/block{i}"
             t, steps = f, []
             for j in range(len(m.block_kernels)):
-                t, b_ = self.conv(f"{b}/conv{j}/kernel", t, m.block_activation[j], f"{b}/bn{j}" if j >= 1 and m.use_bn else None)
-                steps.append(b_)
+                t = push(steps, self.conv(f"{b}/conv{j}/kernel", t, m.block_activation[j], f"{b}/bn{j}" if j >= 1 and m.use_bn else None))
                 if j == 1 and m.add_gates:
-                    t, b_ = self.gate_step(b, t)
-                    steps.append(b_)
+                    t = push(steps, self.gate_step(b, t))
             ds_ = drop_scale.get((pre, i))
             if m.add_multiplier or ds_ is not None:                  # Multiplier, RandomOnOff in front of the Add (:219-225)
-                t, b_ = self.mult_step(f"{b}/multiplier/w0" if m.add_multiplier else None, t, ds_)
-                steps.append(b_)
+                t = push(steps, self.mult_step(f"{b}/multiplier/w0" if m.add_multiplier else None, t, ds_))
             f = ops.add(f, t)
 
             def b_block(dout, steps=steps):
@@ -117,12 +90,11 @@ class UnetBackboneTrainGraph(GenericResnetTrainGraph):
         cmax = 2 * max([m.filters] + m.block_filters)
         ops = self._begin(grads, max(8 * 1024 * 1024, int(L.bf_op_denoiser_loss_scratch_floats(B, H, Wd, m.out_channels)) + 1024,
                                      npix * 4, int(L.bf_op_gate_scratch_floats(B, cmax)) + 64, int(L.bf_op_bn_train_scratch_floats(cmax)) + 64))
-        f32 = self.f32
 
         # -- forward -------------------------------------------------------------------------------------------------------------
         Lv = m.no_levels
         ea = m.entry_activation
-        f, b_base = self.base_step(noisy)
+        f, b_base = self.base_step(noisy, m.kernel_size, m.base_activation)
         b_init = None
         if m.add_initial_bn:
             f, b_init = self.bn_step("initial_bn", f, "linear")
@@ -169,15 +141,9 @@ class UnetBackboneTrainGraph(GenericResnetTrainGraph):
             if small is None:                                        # the deepest level: the entry read the skip alone
                 dskip[lv] = g
                 break
-            Bs, hs, ws, cu = small
-            cs = skips[lv].shape[-1]
-            dup, ds_ = torch.empty((Bs, 2 * hs, 2 * ws, cu), **f32), torch.empty_like(skips[lv])
-            rows = Bs * 4 * hs * ws
-            call("bf_op_slice_channels", N.ptr(g), N.ptr(dup), rows, cu + cs, 0, cu, N.stream_ptr(g))
-            call("bf_op_slice_channels", N.ptr(g), N.ptr(ds_), rows, cu + cs, cu, cs, N.stream_ptr(g))
-            dskip[lv] = ds_
-            g = torch.empty(small, **f32)
-            call("bf_op_upsample2x_bwd", N.ptr(dup), N.ptr(g), Bs, hs, ws, cu, 0, N.stream_ptr(dup))
+            cu = small[-1]
+            dup, dskip[lv] = ops.slice_channels(g, 0, cu), ops.slice_channels(g, cu, g.shape[-1] - cu)
+            g = ops.upsample2x_bwd(dup, False)
         g = dskip[Lv - 1]
         for lv in reversed(range(Lv)):                               # encoder, deepest first
             pooled_from, b_entry, b_blocks = enc[lv]
@@ -185,10 +151,7 @@ class UnetBackboneTrainGraph(GenericResnetTrainGraph):
             if lv == 0:
                 break
             g = b_entry(g)                                           # d pooled
-            dx = torch.empty_like(pooled_from)
-            Bq, Hq, Wq, Cq = pooled_from.shape
-            call("bf_op_maxpool2_bwd", N.ptr(pooled_from), N.ptr(g), N.ptr(dx), Bq, Hq, Wq, Cq, N.stream_ptr(g))
-            g = ops.add(dx, dskip[lv - 1])                           # the skip's two consumers
+            g = ops.add(ops.maxpool2_bwd(pooled_from, g), dskip[lv - 1])     # the skip's two consumers
         if b_init is not None:
             g = b_init(g)
         b_base(g)

@@ -260,6 +260,16 @@ def test_train_step_with_the_concatenate_decoder(depth, width, backbone):
     _check_step(spec, params, model, clean, noisy, LOSS_V5, [1.0, 0.6, 0.3][:depth], depth_scale=ds)
 
 
+def test_use_concat_with_attention_gates_is_refused():
+    """the gate branch never concatenates, so the 2 C-shaped mix / dec kernels of use_concat would meet C channels: the graph
+    refuses the pair like its other unsupported options (the model builder refuses it too, so the flag is set on a built model)"""
+    cfg, spec, params, model, clean, noisy = _setup(3, 1, 32, 32, backbone={"use_attention_gates": True})
+    UnetTrainGraph(model, LOSS_V5)
+    model.use_concat = True
+    with pytest.raises(NotImplementedError, match="use_concat with use_attention_gates"):
+        UnetTrainGraph(model, LOSS_V5)
+
+
 def test_train_step_with_stochastic_depth_and_attention_dropout():
     """training-mode randomness as explicit inputs: per-sample StochasticDepth scales (0 or 1 / (1 - rate)) and the attention's
     dropout keep-mask / keep-probability"""
