@@ -3,8 +3,7 @@
 // activations against <2 % of the FLOPs), so they are plain VALU kernels with 16-byte accesses.
 #include "bf_common.h"
 #include "block_reduce.h"
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+#include "h3v_core.h"          // h8, h3_stream_load16: the head reads the split-planar activation with the stream's load policy
 
 // ------------------------------------------------------------------------------------------
 // base convolution: [cast] -> [virtual pad_to_power_of_2] -> normalise -> conv k x k, Cin -> 16
@@ -306,15 +305,15 @@ __global__ __launch_bounds__(256) void head_kernel(HeadArgs a)
         if (a.feat_split) {
             const int64_t hw = (int64_t)a.H * a.W;
             const char* base = reinterpret_cast<const char*>(a.feat) + (int64_t)b * hw * 64 + ((int64_t)y * a.W + x) * 16;
-            const h8 hi0 = *reinterpret_cast<const h8*>(base), hi1 = *reinterpret_cast<const h8*>(base + hw * 16);
+            const h8 hi0 = h3_stream_load16(base), hi1 = h3_stream_load16(base + hw * 16);
             h8 lo0, lo1;
             if (a.feat_split == 2) {
                 const char* lob = reinterpret_cast<const char*>(a.feat) + (int64_t)b * hw * 64 + hw * 32 + ((int64_t)y * a.W + x) * 8;
                 lo0 = bf_h3c_decode8(*reinterpret_cast<const bf_u2*>(lob));
                 lo1 = bf_h3c_decode8(*reinterpret_cast<const bf_u2*>(lob + hw * 8));
             } else {
-                lo0 = *reinterpret_cast<const h8*>(base + hw * 32);
-                lo1 = *reinterpret_cast<const h8*>(base + hw * 48);
+                lo0 = h3_stream_load16(base + hw * 32);
+                lo1 = h3_stream_load16(base + hw * 48);
             }
             bool finite = true;
 #pragma unroll

@@ -301,8 +301,7 @@ struct H3VRoleC {
                     if (!col_ok[j]) src = reinterpret_cast<const char*>(a.zeros);
                 }
                 char* dst = tin + plane * Gm::IN_PLANE + slot * Gm::PITCH + (1 + 64 * j) * 16;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+                h3_dma16(src, dst);
             }
         }
     }
@@ -369,14 +368,15 @@ struct H3VRoleC {
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
             const int plane = plane0 + pl;
-            char* base = reinterpret_cast<char*>(a.out) + t.img + (size_t)plane * plane_g + (size_t)t.y(o) * a.W * 16;
+            char* image = reinterpret_cast<char*>(a.out) + t.img;
+            const size_t row_off = (size_t)plane * plane_g + (size_t)t.y(o) * a.W * 16;      // wave-uniform, < 2^32
             h8 rec[Gm::PIECES];
 #pragma unroll
             for (int j = 0; j < Gm::PIECES; ++j)
                 rec[j] = *reinterpret_cast<const h8*>(tout + oslot * Gm::OUT_SLOT + plane * Gm::OUT_PLANE + (64 * j + lane) * 16);
 #pragma unroll
             for (int j = 0; j < Gm::PIECES; ++j) {
-                if (FULLW || col_ok[j]) *reinterpret_cast<h8*>(base + col_off[j]) = rec[j];
+                if (FULLW || col_ok[j]) h3_stream_store16(image, (a.compact ? 3u : 4u) * plane_g, row_off, col_off[j], rec[j]);
             }
         }
     }

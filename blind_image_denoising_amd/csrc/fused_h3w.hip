@@ -429,9 +429,7 @@ struct H3WMem<1> {
             const char* src = ok ? reinterpret_cast<const char*>(a.in) + t.img + (size_t)plane * plane_g + (size_t)y * a.W * 16 + col_off
                                  : reinterpret_cast<const char*>(a.zeros);
             char* dst = tin + plane * Gm::X0_PLANE + slot * Gm::PITCH + (1 + 64 * piece) * 16;
-            if (active)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            if (active) h3_dma16(src, dst);
         }
     }
     static constexpr int INFLIGHT = 2 * 4;             // pieces of the two rows younger than the one awaited
@@ -467,10 +465,11 @@ struct H3WMem<2> {
     bool okc[3];
     h8 rec[3];
     bool have;
-    char* grow;
+    char* image;                 // the unit's image in a.out
+    size_t row_off;              // byte offset of the output row inside a plane (< 2^32)
 
     __device__ __forceinline__ H3WMem(const FusedH3WArgs& a_, char*, const char* tout_, const int rw, const unsigned pg)
-        : a(a_), tout(tout_), first(3 * rw), np(rw < 2 ? 3 : 2), plane_g(pg), have(false), grow(nullptr) {}
+        : a(a_), tout(tout_), first(3 * rw), np(rw < 2 ? 3 : 2), plane_g(pg), have(false), image(nullptr), row_off(0) {}
     __device__ __forceinline__ void set_tile(const H3WTile& t, const int lane)
     {
 #pragma unroll
@@ -488,7 +487,8 @@ struct H3WMem<2> {
         const int k = s - Gm::LEAD, oslot = (PH + 1) % Gm::NRO;
         have = (k >= 0) & (k < t.nrows) & !(H3V_ABLATE & 2);                          // wave-uniform
         if (!have) return;
-        grow = reinterpret_cast<char*>(a.out) + t.img + (size_t)t.y(k) * a.W * 16;
+        image = reinterpret_cast<char*>(a.out) + t.img;
+        row_off = (size_t)t.y(k) * a.W * 16;
 #pragma unroll
         for (int i = 0; i < 3; ++i)
             if (i < np) rec[i] = *reinterpret_cast<const h8*>(tout + oslot * Gm::OUT_SLOT + st_off[i]);
@@ -498,7 +498,7 @@ struct H3WMem<2> {
         if (!have) return;
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-            if (okc[i]) *reinterpret_cast<h8*>(grow + g_off[i]) = rec[i];
+            if (okc[i]) h3_stream_store16(image, 4u * plane_g, row_off, g_off[i], rec[i]);
     }
     __device__ __forceinline__ void end() {}
     __device__ __forceinline__ void finish() {}

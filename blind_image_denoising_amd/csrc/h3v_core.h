@@ -10,6 +10,17 @@
 #ifndef H3V_ABLATE
 #define H3V_ABLATE 0
 #endif
+// cache policy of the activation stream (every byte is used once per launch), build constants for A/B builds
+// (tools/ablate_unit.sh fused_h3w H3_LOAD_POLICY 0, tools/stream_policy_variants.sh): the instruction's aux bits, 0 = plain, 2 = nt, 16 = sc1 (write-through for a
+// store), 18 = both.  The results are the same bytes under every policy.  Defaults: nt loads, write-through stores -- the one
+// combination of the eight whose worst A/B round beat the parent's best (profiles/r06_stream_policy_ab.txt).
+#ifndef H3_LOAD_POLICY
+#define H3_LOAD_POLICY 2
+#endif
+#ifndef H3_STORE_POLICY
+#define H3_STORE_POLICY 16
+#endif
+static_assert((H3_LOAD_POLICY & ~18) == 0 && (H3_STORE_POLICY & ~18) == 0, "aux bits: 2 = nt, 16 = sc1");
 #ifndef H3V_PRIO_B
 #define H3V_PRIO_B 1
 #endif
@@ -62,6 +73,37 @@ __device__ __forceinline__ void h3v_barrier()
 #endif
 
 __device__ __forceinline__ int h3v_wrap(const int v, const int n) { return v >= n ? v - n : v; }
+
+// 16 bytes per lane from global memory straight into LDS, with the load policy
+__device__ __forceinline__ void h3_dma16(const char* src, char* dst)
+{
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst,
+                                     16, 0, H3_LOAD_POLICY);
+}
+
+// 16 bytes per lane of the activation stream into registers (head_kernel, edge_layers.hip): the nt bit of the load policy
+__device__ __forceinline__ h8 h3_stream_load16(const char* src)
+{
+    if constexpr (H3_LOAD_POLICY & 2) return __builtin_nontemporal_load(reinterpret_cast<const h8*>(src));
+    else return *reinterpret_cast<const h8*>(src);
+}
+
+// One 16-byte record of an output row to global memory, with the store policy: image = the image's first byte, image_bytes = its
+// planes (< 2^32, the launchers refuse more), row_off = the wave-uniform byte offset of the row inside the image, lane_off = the
+// lane's offset from there (row_off + lane_off + 16 <= image_bytes).  sc1 has no spelling on a C++ store: such a policy goes through a raw buffer resource that spans
+// exactly the image (a record outside it would be dropped without a fault; the callers' column and row guards hold under every policy).
+__device__ __forceinline__ void h3_stream_store16(char* image, const unsigned image_bytes, const size_t row_off, const unsigned lane_off, const h8 v)
+{
+    if constexpr (H3_STORE_POLICY == 0) {
+        *reinterpret_cast<h8*>(image + row_off + lane_off) = v;
+    } else if constexpr (H3_STORE_POLICY == 2) {
+        __builtin_nontemporal_store(v, reinterpret_cast<h8*>(image + row_off + lane_off));
+    } else {
+        typedef unsigned h3_u4 __attribute__((ext_vector_type(4)));
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(image, 0, (int)image_bytes, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(h3_u4, v), rsrc, (int)lane_off, (int)row_off, H3_STORE_POLICY);
+    }
+}
 
 // Epilogue of one 16-pixel group as single-instruction micro-ops, so that they can be placed one by one in the shadows
 // of the NEXT group's MFMAs (an MFMA holds the vector-issue port for half of its 16 cycles; an in-order wave gets its other
