@@ -17,17 +17,19 @@
 //
 //   * 12 waves = 4 roles x 3 waves, three matrix waves per SIMD; wave k of a role owns grid columns [48k, 48k+48) = three MFMA
 //     groups and holds ONE kernel's weights (52 VGPRs).  A1 = conv1a, B1 = conv2a (+ residual x0, folded BN) -> x1 ring,
-//     A2 = conv1b, B2 = conv2b (+ residual x1) -> staging rows;
+//     A2 = conv1b, B2 = conv2b (+ residual x1) -> global memory (H3W_DIRECT_STORE; a launch with the head, or a build with the
+//     constant 0: -> staging rows);
 //   * the memory instructions ride on matrix waves: the A2 waves request x0 row s+3 by LDS-DMA (four 1-KiB pieces each),
-//     the A1 waves store the staged output row (loads and stores on DIFFERENT waves: `s_waitcnt vmcnt(N)` counts both and
-//     stores retire early, see fused_h3v.hip);
+//     the B2 waves store their own records of the output row, 8 bytes per lane, six wave-instructions per wave and step (loads
+//     and stores on DIFFERENT waves: `s_waitcnt vmcnt(N)` counts both and stores retire early, see fused_h3v.hip; with the
+//     staging rows the A1 waves store, 16 bytes per lane);
 //   * LDS rings (ring column = grid column + 1; ring columns 0 and 145 are never written: the zero padding at an image
-//     edge): x0 5 rows, first intermediate 2, x1 3, second intermediate 2, staging 2 -> 131 KB;
+//     edge): x0 5 rows, first intermediate 2, x1 3, second intermediate 2 -> 112 KiB; + 2 staging rows where they exist -> 130 KiB;
 //   * step s, band-relative rows (x0 row k is consumed at step k+4): A1 turns x0 row s-4 into its three vertical-tap
 //     contributions and completes intermediate row s-5; B1 consumes intermediate row s-6 and completes x1 row s-7 (its
 //     accumulator starts as the residual (s2 I) x [x_hi | x_lo] on top of the folded shift); A2 consumes x1 row s-8 ->
-//     second intermediate row s-9; B2 consumes it in step s+1 and completes output row s-11 in step s; stored in s+1.
-//     ONE barrier per step, nrows + 12 steps per band;
+//     second intermediate row s-9; B2 consumes it in step s+1 and completes AND stores output row s-11 in step s (staged: the
+//     storer stores it in s+1).  ONE barrier per step, nrows + 12 steps per band;
 //   * rows and columns outside the image are forced to zero in every ring (they are the NEXT convolution's zero padding,
 //     not values computed from padded input);
 //   * the FIRST launch of a forward on uint8 images (FusedH3WArgs::base_u8, template parameter BASE) has no loader: it computes
@@ -82,6 +84,14 @@
 #define H3W_XCD_ORDER 1
 #endif
 
+// where a finished output row leaves the workgroup (a launch with the head, H3WMem<3>, always stages: its storer reads whole pixels):
+// 0 = B2 writes it to the staging rows and the A1 waves read it back one step later and store it (16-byte records);
+// 1 = B2 stores its own 8-byte half-records from registers, in the MFMA shadows where the two ds_write_b64 of a group sat: no staging
+//     rows, no storer hook, 17 KB less LDS traffic per row step (same-box A/B: DESIGN 4.1c, profiles/r07_direct_store_ab.txt)
+#ifndef H3W_DIRECT_STORE
+#define H3W_DIRECT_STORE 1
+#endif
+
 struct H3WGeom {
     static constexpr int NG = 9, GW = 16 * NG;         // grid: nine 16-column groups
     static constexpr int G = 3;                        // groups per matrix wave
@@ -95,7 +105,10 @@ struct H3WGeom {
     static constexpr int X1_PLANE = (NRX1 * PITCH + 255) / 256 * 256;
     static constexpr int OUT_PLANE = GW * 16, OUT_SLOT = 4 * OUT_PLANE;       // staging rows are indexed by GRID column too
     static constexpr int X0_OFF = 0, M1_OFF = X0_OFF + 4 * X0_PLANE, X1_OFF = M1_OFF + 4 * M_PLANE, M2_OFF = X1_OFF + 4 * X1_PLANE;
-    static constexpr int OUT_OFF = M2_OFF + 4 * M_PLANE, LDS_BYTES = OUT_OFF + NRO * OUT_SLOT;
+    // the staging rows exist where a storer reads them back: in every launch of an H3W_DIRECT_STORE 0 build, else in the head launch
+    // alone (LDS_BYTES_STAGED); the other launches end at the rings (112 KiB) and the producer's tables follow there
+    static constexpr int OUT_OFF = M2_OFF + 4 * M_PLANE, LDS_BYTES_STAGED = OUT_OFF + NRO * OUT_SLOT;
+    static constexpr int LDS_BYTES = H3W_DIRECT_STORE ? OUT_OFF : LDS_BYTES_STAGED;
     // producer launch only (H3WProducer, behind the rings): the [r, g, b, 1_inside] records of four input rows, each row twice
     // (the second copy shifted by one pixel, as in base_rows.hip), the base convolution's A operands + 1 / s, reduction scratch
     static constexpr int BIN_RING = 4, BIN_ROWPX = GW + 4;       // ring pixel j = image column G0 - 1 + j; j <= GW + 1 are written
@@ -107,7 +120,7 @@ struct H3WGeom {
     static constexpr int NSTAMP = 4;
     static_assert(UNROLL % NRM == 0 && UNROLL % NRO == 0 && UNROLL % NRX1 == 0 && UNROLL % 3 == 0, "static slots");
     static_assert(NRX0 == PD + 2, "x0 ring: rows s-1 (residual), s (conv1a), s+1 (landed), s+2, s+3 (in flight)");
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+    static_assert(LDS_BYTES_STAGED <= 160 * 1024 && LDS_BYTES <= LDS_BYTES_STAGED && LDS_BYTES % 16 == 0 && LDS_BYTES_STAGED % 16 == 0, "LDS");
     static_assert(3 * X0_PLANE + NRX0 * PITCH < 65536, "fragment offsets fit the 16-bit ds offset");
 };
 
@@ -241,9 +254,40 @@ struct H3WRoleA {
 // ---------------------------------------------------------------------------------------------------------------------
 // role B: a block's second convolution + folded BN + residual.  B1 writes the x1 ring, B2 the staging rows.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int RESP, int OUTP>      // plane strides of the ring the residual comes from and of the ring / staging row written
-struct H3WRoleB {
+// The epilogue of a role that stores its output row itself (B2 under H3W_DIRECT_STORE): micro-ops 0 .. 7 of H3VEpi<false>, then the lane's
+// two 8-byte records (hi, lo) go to global memory where micro-ops 8 and 9 wrote them to LDS -- behind the sixth MFMA of the next group,
+// the last group's at the end of the step.  mask: the lanes that store -- the row is one of the band's (else 0) and the lane's column one
+// of the strip's; a wave-uniform lane mask, so the guard is one scalar instruction on the execution mask and no vector one.
+struct H3WEpiStore : H3VEpi<false> {
+    char* image;
+    unsigned image_bytes, off;   // off: the lane's byte offset inside the image's first row (plane, column, half-record)
+    size_t row_hi, row_lo;       // wave-uniform byte offsets of the row in the lane's hi plane pair and in its lo pair (+ 2 planes)
+    unsigned long long mask;
+    __device__ __forceinline__ void store()
+    {
+        if (__builtin_amdgcn_inverse_ballot_w64(mask)) {
+            h3_stream_store8(image, image_bytes, row_hi, off, (H3V_ABLATE & 64) ? (h3v_u2){__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y)} : (h3v_u2){h0, h1});
+            h3_stream_store8(image, image_bytes, row_lo, off, (H3V_ABLATE & 64) ? (h3v_u2){__builtin_bit_cast(unsigned, v.z), __builtin_bit_cast(unsigned, v.w)} : (h3v_u2){l0, l1});
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    template <int SLOT> __device__ __forceinline__ void pair()
+    {
+        if constexpr (SLOT < 4) H3VEpi<false>::template pair<SLOT>();
+        else if constexpr (SLOT == 4) store();
+    }
+    __device__ __forceinline__ void all()
+    {
+        pair<0>(); pair<1>(); pair<2>(); pair<3>(); pair<4>();
+    }
+};
+template <bool DIRECT> struct H3WEpiOf { using type = H3VEpi<false>; };
+template <> struct H3WEpiOf<true> { using type = H3WEpiStore; };
+
+template <int RESP, int OUTP, bool DIRECT = false>      // plane strides of the ring the residual comes from and of the ring / staging row written;
+struct H3WRoleB {                                       // DIRECT: no LDS output, the role stores its rows to global memory
     using Gm = H3WGeom;
+    using Epi = typename H3WEpiOf<DIRECT>::type;
     const char* tmid;
     const char* tres;
     char* tout;
@@ -256,11 +300,27 @@ struct H3WRoleB {
     f32x4 shs;                   // folded BN shift of the lane's four channels times s2 (the accumulators' scale)
     float lane_scale[Gm::G];
     bool skip_last = false;      // timing experiment (H3V_ABLATE & 256)
+    // DIRECT only
+    char* gout;                  // FusedH3WArgs::out
+    char* image;                 // the unit's image in it
+    unsigned plane_g;            // bytes per global plane
+    unsigned go;                 // lane's byte offset of its hi record inside the image's first row, group 0 (group g: + 256 g; lo: + 2 planes)
+    unsigned long long okm[Gm::G];      // the lanes whose column of group g is an output column of the strip, inside [X0, X1) (wave-uniform)
+    bool have;                   // the row this step completes is one of the band's (wave-uniform)
+    size_t row_hi, row_lo;       // its byte offset inside a plane / + 2 planes (wave-uniform, < 2^32)
 
     __device__ __forceinline__ void init(const void* wimg, const FusedH3WArgs& a, const float* aux, const int lane, const int gc0,
                                          const bool out_is_ring)
     {
         const int q = lane >> 4;
+        gout = reinterpret_cast<char*>(a.out);
+        plane_g = (unsigned)a.H * (unsigned)a.W * 16u;
+        image = nullptr;
+        go = 0;
+        have = false;
+        row_hi = row_lo = 0;
+#pragma unroll
+        for (int g = 0; g < Gm::G; ++g) okm[g] = 0;
 #pragma unroll
         for (int i = 0; i < 13; ++i) w[i] = reinterpret_cast<const h8*>(wimg)[bf_band_wimage(a, i) * 64 + lane];
         inv_s2 = aux[48];
@@ -278,6 +338,23 @@ struct H3WRoleB {
     {
 #pragma unroll
         for (int g = 0; g < Gm::G; ++g) lane_scale[g] = (t.G0 + gc0 + 16 * g < W) ? inv_s2 : 0.f;
+        if constexpr (DIRECT) {
+            // the halo groups of the strip's grid, the columns right of a ragged strip and of the image: not stored
+            const int q = (threadIdx.x & 63) >> 4, c0 = t.G0 + gc0;
+#pragma unroll
+            for (int g = 0; g < Gm::G; ++g) okm[g] = __builtin_amdgcn_ballot_w64((c0 + 16 * g >= t.X0) & (c0 + 16 * g < t.X1));
+            go = (unsigned)(q >> 1) * plane_g + (unsigned)c0 * 16u + (unsigned)(q & 1) * 8u;
+            image = gout + t.img;
+        }
+    }
+    // DIRECT: band-relative row k is the output row this step completes
+    __device__ __forceinline__ void set_row(const H3WTile& t, const int W, const int k)
+    {
+        if constexpr (DIRECT) {
+            have = (k >= 0) & (k < t.nrows) & !(H3V_ABLATE & 2);                      // wave-uniform
+            row_hi = (size_t)t.y(have ? k : 0) * W * 16;
+            row_lo = row_hi + 2 * (size_t)plane_g;
+        }
     }
 
     __device__ __forceinline__ H3VFrag load(const int mslot, const int g) const
@@ -295,14 +372,25 @@ struct H3WRoleB {
     }
 
     // the accumulator already holds s2 * (scale * conv2 + x + shift) (the shift is the C operand of the row's first MFMA)
-    __device__ __forceinline__ H3VEpi<false> epilogue(const int g, const int oslot_bytes, const f32x4 accv, const bool rowok) const
+    __device__ __forceinline__ Epi epilogue(const int g, const int oslot_bytes, const f32x4 accv, const bool rowok) const
     {
-        H3VEpi<false> e;
+        Epi e;
         e.v = accv;
         e.sc = rowok ? lane_scale[g] : 0.f;
         e.floor_ = 0.f;
-        e.p = tout + wo + oslot_bytes + g * 256;
-        e.lo_off = 2 * OUTP;
+        if constexpr (DIRECT) {
+            e.p = nullptr;
+            e.lo_off = 0;
+            e.image = image;
+            e.image_bytes = 4u * plane_g;
+            e.off = go + 256u * g;
+            e.row_hi = row_hi;
+            e.row_lo = row_lo;
+            e.mask = have ? okm[g] : 0ull;
+        } else {
+            e.p = tout + wo + oslot_bytes + g * 256;
+            e.lo_off = 2 * OUTP;
+        }
         return e;
     }
 
@@ -352,10 +440,10 @@ struct H3WRoleB {
             __builtin_amdgcn_sched_barrier(0);
             f32x4 c0;
             if (g > 0) {
-                H3VEpi<false> e = epilogue(g - 1, oslot_bytes, acc[g - 1][a2], rowok);
+                Epi e = epilogue(g - 1, oslot_bytes, acc[g - 1][a2], rowok);
                 mfmas<0>(g, a1, a2, cur, xr, c0, &e);
             } else {
-                mfmas<0>(g, a1, a2, cur, xr, c0, (H3VEpi<false>*)nullptr);
+                mfmas<0>(g, a1, a2, cur, xr, c0, (Epi*)nullptr);
                 hook.after_first_group();
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -365,7 +453,7 @@ struct H3WRoleB {
                 xr = xn;
             }
         }
-        H3VEpi<false> e = epilogue(Gm::G - 1, oslot_bytes, bf_acc_ready(acc[Gm::G - 1][a2]), rowok);
+        Epi e = epilogue(Gm::G - 1, oslot_bytes, bf_acc_ready(acc[Gm::G - 1][a2]), rowok);
         e.all();
     }
 };
@@ -375,13 +463,17 @@ struct H3WRoleB {
 // KIND 1, the loader: LDS-DMA of the x0 rows.  Wave j of its role moves piece j (grid columns [64j, 64j+64), the third piece 16
 // columns) of all four planes: four wave-instructions per step, EVERY step (rows outside the band / the image read the zero
 // line), so that the vmcnt of the wait is a constant.
-// KIND 2, the storer: the staged output row -> global memory.  Eight 1-KiB pieces (plane, half) per row; wave j moves pieces
-// 3j .. 3j+2.  The staging reads are issued at the start of the step, the stores behind the first group's MFMAs.
-// Loads and stores sit on DIFFERENT waves: `s_waitcnt vmcnt(N)` counts both and stores retire early (fused_h3v.hip).
+// KIND 2, the storer (only where the staging rows exist and no head: H3W_DIRECT_STORE 0): the staged output row -> global memory.
+// Eight 1-KiB pieces (plane, half) per row; wave j moves pieces 3j .. 3j+2.  The staging reads are issued at the start of the
+// step, the stores behind the first group's MFMAs.
+// Loads and stores sit on DIFFERENT waves: `s_waitcnt vmcnt(N)` counts both and stores retire early (fused_h3v.hip).  Under
+// H3W_DIRECT_STORE the stores are B2's own (H3WEpiStore), so H3W_MEM_ROLES only places the loader; its value 3 would put the loads on B2
+// as well and is refused.
 // ---------------------------------------------------------------------------------------------------------------------
 #ifndef H3W_MEM_ROLES
 #define H3W_MEM_ROLES 0          // which roles carry {loader, storer}: 0 = {A2, A1}, 1 = {A1, B1}, 2 = {B1, A1}, 3 = {B2, A1}
 #endif
+static_assert(!(H3W_DIRECT_STORE && H3W_MEM_ROLES == 3), "loads and stores on different waves");
 constexpr int h3w_mem_kind(const int role)
 {
     constexpr int loader[4] = {2, 0, 1, 3}, storer[4] = {0, 1, 0, 0};
@@ -597,7 +689,7 @@ struct H3WMem<3> {
 #ifndef H3W_BASE_SPREAD
 #define H3W_BASE_SPREAD 1        // 0 = the A2 waves produce three groups each; 1 = one group per wave of B1, A2, B2; 2 = of A1, B1, A2
 #endif
-// groups per wave of a role / the first group of its wave rw / the role whose waves fetch the pixels (never A1: it stores)
+// groups per wave of a role / the first group of its wave rw / the role whose waves fetch the pixels (never a role that stores: A1 with the staging rows, B2 without)
 constexpr int h3w_base_groups(const int role)
 {
     return H3W_BASE_SPREAD == 0 ? (role == 2 ? 3 : 0) : (H3W_BASE_SPREAD == 1 ? (role >= 1 ? 1 : 0) : (role <= 2 ? 1 : 0));
@@ -735,12 +827,15 @@ struct H3WProducer<0, false> {     // a wave without a share, and every wave of 
     __device__ __forceinline__ void begin(const H3WTile&, int) {}
 };
 
-// the hook of a role: the head storer replaces the storer in a HEAD launch; a BASE launch has no loader
+// the hook of a role: the head storer replaces the storer in a HEAD launch; a BASE launch has no loader; where B2 stores its rows itself
+// (h3w_direct) there is no storer
+template <bool HEAD>
+constexpr bool h3w_direct() { return H3W_DIRECT_STORE != 0 && !HEAD; }
 template <bool HEAD, bool BASE>
 constexpr int h3w_hook_kind(const int role)
 {
     const int k = h3w_mem_kind(role);
-    return (HEAD && k == 2) ? 3 : ((BASE && k == 1) ? 0 : k);
+    return k == 2 ? (HEAD ? 3 : (h3w_direct<HEAD>() ? 0 : 2)) : ((BASE && k == 1) ? 0 : k);
 }
 
 template <bool HEAD, bool BASE>
@@ -752,7 +847,9 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
     char* tm1 = h3w_lds + Gm::M1_OFF;                           // [4 planes][2 rows][146][8]
     char* tx1 = h3w_lds + Gm::X1_OFF;                           // [4 planes][3 rows][146][8]
     char* tm2 = h3w_lds + Gm::M2_OFF;                           // [4 planes][2 rows][146][8]
-    char* tout = h3w_lds + Gm::OUT_OFF;                         // [2 rows][4 planes][144 columns][8 f16]
+    constexpr bool DIRECT = h3w_direct<HEAD>();                 // B2 stores its rows itself: no staging rows
+    constexpr int LDS_RINGS = DIRECT ? Gm::LDS_BYTES : Gm::LDS_BYTES_STAGED;
+    char* tout = DIRECT ? nullptr : h3w_lds + Gm::OUT_OFF;      // [2 rows][4 planes][144 columns][8 f16]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15;
@@ -763,7 +860,7 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
     // ring columns 0 and 145 are the zero padding at an image edge: cleared once, never written
     // (a BASE launch: so is everything of the input ring that is never written, the pixel past the last pair among it)
     if (BASE && a.status && blockIdx.x == 0 && tid == 0) *a.status = 0;       // first kernel of a forward
-    for (int i = tid * 16; i < (BASE ? Gm::LDS_BYTES_BASE : Gm::LDS_BYTES); i += Gm::NT * 16)
+    for (int i = tid * 16; i < (BASE ? Gm::LDS_BYTES_BASE : LDS_RINGS); i += Gm::NT * 16)
         *reinterpret_cast<f32x4*>(h3w_lds + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
     __syncthreads();
     if constexpr (BASE) {
@@ -869,9 +966,9 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
 #undef H3W_ACTIVE
 #undef H3W_STEP
     } else {
-        // ---- B2: conv2b + residual x1 -> staging rows
+        // ---- B2: conv2b + residual x1 -> staging rows, or (DIRECT) global memory: output row s - 11 is complete in step s
         __builtin_amdgcn_s_setprio(H3W_PRIO_B2);
-        H3WRoleB<Gm::X1_PLANE, Gm::OUT_PLANE> R;
+        H3WRoleB<Gm::X1_PLANE, Gm::OUT_PLANE, DIRECT> R;
         R.tmid = tm2; R.tres = tx1; R.tout = tout;
         R.init(a.w2r[1], a, a.aux[1], lane, gc0, false);
         R.skip_last = (H3V_ABLATE & 256) && rw == Gm::NR - 1;
@@ -879,7 +976,7 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         H3WProducer<BASE ? h3w_base_groups(3) : 0, BASE && h3w_base_groups(3) && h3w_base_fetches(3)> P(a, h3w_lds, h3w_base_first_group(3, rw), rw);
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));
 #define H3W_ACTIVE(s) (((s) >= 9) & ((s) < t.nrows + 11))
-#define H3W_STEP(PH) R.template step<PH>(((PH + 1) % Gm::NRX1) * Gm::PITCH, (PH % Gm::NRO) * Gm::OUT_SLOT, true, M)
+#define H3W_STEP(PH) R.set_row(t, a.W, s - (Gm::LEAD - 1)); R.template step<PH>(((PH + 1) % Gm::NRX1) * Gm::PITCH, (PH % Gm::NRO) * Gm::OUT_SLOT, true, M)
         H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP)
 #undef H3W_ACTIVE
 #undef H3W_STEP
@@ -917,7 +1014,7 @@ hipError_t bf_launch_fused_block2_h3w(const FusedH3WArgs& args, hipStream_t s)
     if (a.head_wh && (!a.head_out || a.Ho < 1 || a.Wo < 1 || a.Ho > a.H || a.Wo > a.W)) return hipErrorInvalidValue;
     void (*kernel)(FusedH3WArgs) = a.base_u8 ? fused_block2_h3w_kernel<false, true>
                                    : a.head_wh ? fused_block2_h3w_kernel<true, false> : fused_block2_h3w_kernel<false, false>;
-    const int lds = a.base_u8 ? Gm::LDS_BYTES_BASE : Gm::LDS_BYTES;
+    const int lds = a.base_u8 ? Gm::LDS_BYTES_BASE : (a.head_wh ? Gm::LDS_BYTES_STAGED : Gm::LDS_BYTES);
     const hipError_t e = bf_set_max_lds(reinterpret_cast<const void*>(kernel), lds);      // once per device
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(Gm::NT), lds, s, a);

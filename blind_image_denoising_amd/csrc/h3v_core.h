@@ -105,6 +105,21 @@ __device__ __forceinline__ void h3_stream_store16(char* image, const unsigned im
     }
 }
 
+// The 8-byte twin (fused_h3w.hip: a lane of the last role stores its own half-record, 4 channels, hi or lo): the same arguments
+// with row_off + lane_off + 8 <= image_bytes, the same policies.  A wave of 16 columns x 4 quarters writes two whole 256-byte runs.
+typedef unsigned h3v_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void h3_stream_store8(char* image, const unsigned image_bytes, const size_t row_off, const unsigned lane_off, const h3v_u2 v)
+{
+    if constexpr (H3_STORE_POLICY == 0) {
+        *reinterpret_cast<h3v_u2*>(image + row_off + lane_off) = v;
+    } else if constexpr (H3_STORE_POLICY == 2) {
+        __builtin_nontemporal_store(v, reinterpret_cast<h3v_u2*>(image + row_off + lane_off));
+    } else {
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(image, 0, (int)image_bytes, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b64(v, rsrc, (int)lane_off, (int)row_off, H3_STORE_POLICY);
+    }
+}
+
 // Epilogue of one 16-pixel group as single-instruction micro-ops, so that they can be placed one by one in the shadows
 // of the NEXT group's MFMAs (an MFMA holds the vector-issue port for half of its 16 cycles; an in-order wave gets its other
 // vector instructions for free only if they sit right there, and hipcc neither interleaves inline asm nor selects the
@@ -114,7 +129,6 @@ __device__ __forceinline__ void h3_stream_store16(char* image, const unsigned im
 //   the image), so hi is the correctly rounded f16 of the value and the scale costs no instruction.
 // Every micro-op reads accumulator registers no earlier than two MFMAs after the MFMA that finished them (the caller's
 // placement), which covers the MFMA -> VALU hazard hipcc does not pad for inline asm.
-typedef unsigned h3v_u2 __attribute__((ext_vector_type(2)));
 template <bool RELU>
 struct H3VEpi {
     static constexpr int NOPS = (RELU ? 4 : 0) + 10;
