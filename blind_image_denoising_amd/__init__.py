@@ -33,8 +33,11 @@ from .file_operations import load_image
 from . import metrics
 from .metrics import ImageMetrics, image_metrics, image_metric_sums, psnr, ssim, mae, evaluate
 from .noise_estimate import NoiseEstimate, noise_statistics, noise_summary, estimate_noise, evaluate_blind
+from . import noise_level
+from .noise_level import NoiseLevelFunction, noise_level_statistics, noise_level_function, camera_noise
 from . import risk
 from .risk import RiskEstimate, risk_probe_stack_u8, risk_sums, estimate_risk, evaluate_blind_risk, format_risk_report
+from .risk import risk_sums_affine, risk_from_affine_sums, estimate_risk_affine
 from . import neighbor
 from .neighbor import neighbor_pairs, NeighborPairs, RiskValidator, parse_self_supervised_config
 from . import regularizers

@@ -74,6 +74,9 @@ SIGNATURES = {
     "bf_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _D, _D, _D, _P, _P, _I64, _P]),
     "bf_noise_estimate_scratch_bytes": (_I64, [_I, _I, _I, _I]),
     "bf_noise_estimate": (_I, [_P, _I, _I, _I, _I, _I, _P, _I64, _P, _P]),
+    "bf_noise_level_scratch_bytes": (_I64, [_I, _I, _I, _I]),
+    "bf_noise_level": (_I, [_P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
+    "bf_op_camera_noise_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, C.c_uint64, _P]),
     "bf_op_pack_pointwise": (_I, [_P, _P, _I, _I, _P]),
     "bf_op_pointwise": (_I, [_P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _F, _P]),
     "bf_op_pointwise_ex": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _F, _I, _P]),
@@ -182,6 +185,8 @@ SIGNATURES = {
     "bf_op_risk_probe_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _P]),
     "bf_op_risk_sums_scratch_bytes": (_I64, [_I, _I, _I, _I, _I]),
     "bf_op_risk_sums": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _P, _I64, _P, _P]),
+    "bf_op_risk_sums_affine_scratch_bytes": (_I64, [_I, _I, _I, _I, _I]),
+    "bf_op_risk_sums_affine": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _P, _I64, _P, _P]),
     "bf_op_neighbor_pairs": (_I, [_P, _I, _P, _F, _P, _P, _I, _I, _I, _I, C.c_uint64, _P]),
     "bf_set_option": (_I, [_P, C.c_char_p, _I]),
     "bf_get_timing": (_I, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),

@@ -22,6 +22,7 @@
 // calls return the same bits, and a plane inside a batch the bits of that plane alone.
 #include "bf_common.h"
 #include "block_reduce.h"
+#include "grouped_median.h"
 #include <math.h>
 #include <type_traits>
 
@@ -32,7 +33,7 @@ constexpr int NE_PX = 64;                 // pixel columns of a tile: one per la
 constexpr int NE_BAND = 32;               // rows of a tile (a workgroup)
 constexpr int NE_SUB = NE_BAND / 4;       // rows of a wave; even, so that a 2x2 cell stays inside one wave
 constexpr int NE_BINS = 511;              // q of a uint8 cell is an integer in 0..510
-constexpr int NE_BINS_PAD = 512;
+constexpr int NE_BINS_PAD = BF_MEDIAN_BINS_PAD;
 
 struct NeTiles {
     int x, y;
@@ -137,37 +138,10 @@ __global__ __launch_bounds__(256) void noise_estimate_finalize_kernel(const A* _
         if (!U8) o[2] = (double)NAN;
     }
     if constexpr (U8) {
-        // grouped-data median of the histogram: inclusive scan of the 512 (padded) bins, two per thread, then the one bin k with
-        // cum(k-1) < n/2 <= cum(k) interpolates: bin 0 covers [0, 1/2), bin k >= 1 covers [k - 1/2, k + 1/2)
+        // grouped-data median of the histogram (grouped_median.h): the bins tid and tid + 256 of the 512 (padded) bins
         const unsigned long long* g = ghist + (int64_t)blockIdx.x * NE_BINS_PAD;
         const unsigned long long hk[2] = {g[tid], g[tid + 256]};
-        cum[tid] = hk[0];
-        cum[tid + 256] = hk[1];
-        __syncthreads();
-        for (int off = 1; off < NE_BINS_PAD; off <<= 1) {
-            unsigned long long v[2];
-            for (int j = 0; j < 2; ++j) {
-                const int i = tid + j * 256;
-                v[j] = cum[i] + (i >= off ? cum[i - off] : 0ull);
-            }
-            __syncthreads();
-            cum[tid] = v[0];
-            cum[tid + 256] = v[1];
-            __syncthreads();
-        }
-        const unsigned long long n = cum[NE_BINS_PAD - 1];
-        const double half = (double)n / 2.0;
-        if (tid == 0 && (n == 0ull || hk[0] == n)) o[2] = 0.0;     // no cell differs from zero: nothing to interpolate
-        if (n != 0ull && g[0] != n)
-            for (int j = 0; j < 2; ++j) {
-                const int k = tid + j * 256;
-                const double before = (double)(cum[k] - hk[j]);
-                if (hk[j] != 0ull && (double)cum[k] >= half && before < half) {
-                    const double lo = k == 0 ? 0.0 : (double)k - 0.5, width = k == 0 ? 0.5 : 1.0;
-                    const double med = lo + width * (half - before) / (double)hk[j];
-                    o[2] = med / 2.0 / 0.6745;
-                }
-            }
+        bf_grouped_median_sigma(hk, cum, o + 2);
     }
 }
 

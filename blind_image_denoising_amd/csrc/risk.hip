@@ -2,7 +2,9 @@
 // n ~ N(0, sigma^2),  E |f(y) - x|^2 / N = E[ |f(y) - y|^2 / N - sigma^2 + (2 sigma^2 / N) div f(y) ], and the divergence comes
 // from a Monte-Carlo probe (Ramani, Blu, Unser 2008): div f(y) ~ b . (f(y + a b) - f(y)) / a with b = +-1 per element.
 //   bf_op_risk_probe_u8: one read of the uint8 batch, member 0 = the batch, member p = 1..K = the batch + a s_p;
-//   bf_op_risk_sums:     per image and channel  R = sum (f_0 - y)^2  and  D_p = sum s_p (f_p - f_0)  over the float results.
+//   bf_op_risk_sums:     per image and channel  R = sum (f_0 - y)^2  and  D_p = sum s_p (f_p - f_0)  over the float results;
+//   bf_op_risk_sums_affine: the same kernel with Y = sum y and Dy_p = sum y s_p (f_p - f_0) next to them, for noise whose variance is
+//                        affine in the signal; R and D_p carry the bits of bf_op_risk_sums.
 // The host side is blind_image_denoising_amd/risk.py; the formulas and the assumptions are DESIGN.md 7.8.
 //
 // Probe sign.  Element e = (h W + w) C + c of an image (image-local: every image of a batch gets the same signs, so an image
@@ -29,6 +31,7 @@ namespace {
 constexpr int RK_MAXC = 4, RK_MAXK = 8, RK_MAXA = 16;
 constexpr int RK_THREADS = 256;                          // block_reduce.h's two-stage sum is built for 256
 constexpr int RK_MAXQ = RK_MAXC * (1 + RK_MAXK);          // quantities per image: [C][1 + K]
+constexpr int RK_MAXQ_AFFINE = RK_MAXC * (2 + 2 * RK_MAXK);      // bf_op_risk_sums_affine: [C][2 + 2 K]
 
 // four probe signs of group j (bit i set: +1 for element 4 j + i), before the reflection
 __device__ __forceinline__ unsigned rk_sign_bits(int64_t j, int p, uint64_t seed)
@@ -116,22 +119,25 @@ int64_t rk_tiles(int64_t n, int C)
     return (units + tile - 1) / tile;
 }
 
-// partial[workgroup][c][0] = sum (f_0 - y)^2, partial[workgroup][c][p] = sum s_p (f_p - f_0) over the tile's elements of channel c
-template <int C>
+// partial[workgroup][c][0] = sum (f_0 - y)^2, partial[workgroup][c][p] = sum s_p (f_p - f_0) over the tile's elements of channel c.
+// AFFINE (bf_op_risk_sums_affine): partial[workgroup][c] = (R, Y = sum y, D_1..K, Dy_1..K), Dy_p = sum y s_p (f_p - f_0).  R and D_p
+// are formed by the same statements in the same order in both forms: they carry the same bits.
+template <int C, bool AFFINE>
 __global__ __launch_bounds__(RK_THREADS) void risk_sums_tile_kernel(const uint8_t* __restrict__ y, const float* __restrict__ f, int B,
                                                                     int64_t n, int tiles, int K, int a, uint64_t seed, int vec,
                                                                     double* __restrict__ partial)
 {
     using U = RkUnit<C>;
-    __shared__ double red[4][RK_MAXQ];
+    __shared__ double red[4][AFFINE ? RK_MAXQ_AFFINE : RK_MAXQ];
+    const int QC = AFFINE ? 2 + 2 * K : 1 + K;                   // quantities per channel
     const int b = blockIdx.x / tiles, tile = blockIdx.x % tiles;
     const uint8_t* __restrict__ yb = y + (int64_t)b * n;
 
     unsigned y4[U::T][U::GROUPS];
     float f0[U::T][U::GROUPS][4];
-    double acc[C];
+    double acc[C], accy[C];                                      // accy: Y, then Dy_p (AFFINE only)
 #pragma unroll
-    for (int c = 0; c < C; ++c) acc[c] = 0.0;
+    for (int c = 0; c < C; ++c) acc[c] = accy[c] = 0.0;
     const float* __restrict__ fb = f + (int64_t)b * n;
 #pragma unroll
     for (int t = 0; t < U::T; ++t) {
@@ -145,6 +151,7 @@ __global__ __launch_bounds__(RK_THREADS) void risk_sums_tile_kernel(const uint8_
             for (int i = 0; i < 4; ++i) {
                 const double d = (double)f0[t][g][i] - (double)(y4[t][g] >> (8 * i) & 255u);       // 0 - 0 past the image
                 acc[(g * 4 + i) % C] += d * d;
+                if constexpr (AFFINE) accy[(g * 4 + i) % C] += (double)(y4[t][g] >> (8 * i) & 255u);       // integers: exact
             }
         }
     }
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(RK_THREADS) void risk_sums_tile_kernel(const uint8_
         if (p > 0) {
             const float* __restrict__ fp = f + ((int64_t)p * B + b) * n;
 #pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = 0.0;
+            for (int c = 0; c < C; ++c) acc[c] = accy[c] = 0.0;
 #pragma unroll
             for (int t = 0; t < U::T; ++t) {
                 const int64_t u = (int64_t)tile * U::TILE_UNITS + t * RK_THREADS + threadIdx.x;
@@ -169,14 +176,18 @@ __global__ __launch_bounds__(RK_THREADS) void risk_sums_tile_kernel(const uint8_
                         rk_probe((int)(y4[t][g] >> (8 * i) & 255u), a, bits >> i & 1u, up);
                         const double d = (double)v[i] - (double)f0[t][g][i];
                         acc[(g * 4 + i) % C] += up ? d : -d;
+                        if constexpr (AFFINE) accy[(g * 4 + i) % C] += (double)(y4[t][g] >> (8 * i) & 255u) * (up ? d : -d);
                     }
                 }
             }
         }
 #pragma unroll
-        for (int c = 0; c < C; ++c) bf_tile_stage(red, c * (1 + K) + p, acc[c]);
+        for (int c = 0; c < C; ++c) {
+            bf_tile_stage(red, c * QC + (AFFINE && p > 0 ? 1 + p : p), acc[c]);
+            if constexpr (AFFINE) bf_tile_stage(red, c * QC + (p > 0 ? 1 + K + p : 1), accy[c]);
+        }
     }
-    const int Q = C * (1 + K);
+    const int Q = C * QC;
     bf_tile_partials(red, Q, partial + (int64_t)blockIdx.x * Q);
 }
 
@@ -204,6 +215,47 @@ int64_t rk_checked_elements(int B, int H, int W, int C, int probes, int amplitud
     return n;
 }
 
+// the checks and the two launches of bf_op_risk_sums (QC = 1 + K quantities per channel) and bf_op_risk_sums_affine (2 + 2 K)
+template <bool AFFINE>
+int64_t rk_sums_scratch_bytes(int B, int H, int W, int C, int probes)
+{
+    const int64_t n = rk_checked_elements(B, H, W, C, probes, 1);
+    if (n == 0) return BF_EINVAL;
+    return rk_tiles(n, C) * B * C * (AFFINE ? 2 + 2 * probes : 1 + probes) * (int64_t)sizeof(double);
+}
+
+template <int C, bool AFFINE>
+void rk_launch_tiles(dim3 grid, hipStream_t s, const uint8_t* y, const float* f, int B, int64_t n, int tiles, int probes, int amplitude,
+                     uint64_t seed, int vec, double* partial)
+{
+    hipLaunchKernelGGL((risk_sums_tile_kernel<C, AFFINE>), grid, dim3(RK_THREADS), 0, s, y, f, B, n, tiles, probes, amplitude, seed, vec,
+                       partial);
+}
+
+template <bool AFFINE>
+int rk_sums(const uint8_t* y, const float* f, int B, int H, int W, int C, int probes, int amplitude, uint64_t seed, void* scratch,
+            int64_t scratch_bytes, double* out, void* stream)
+{
+    const int64_t n = rk_checked_elements(B, H, W, C, probes, amplitude);
+    if (!y || !f || !scratch || !out || n == 0) return BF_EINVAL;
+    if (scratch_bytes < rk_sums_scratch_bytes<AFFINE>(B, H, W, C, probes) || ((uintptr_t)scratch | (uintptr_t)out) % 8 || (uintptr_t)f % 4)
+        return BF_EINVAL;
+    const int tiles = (int)rk_tiles(n, C);
+    const int vec = n % 4 == 0 && (uintptr_t)y % 4 == 0 && (uintptr_t)f % 16 == 0;
+    const dim3 grid((unsigned)(tiles * B));
+    hipStream_t s = (hipStream_t)stream;
+    double* partial = (double*)scratch;
+    switch (C) {
+    case 1: rk_launch_tiles<1, AFFINE>(grid, s, y, f, B, n, tiles, probes, amplitude, seed, vec, partial); break;
+    case 2: rk_launch_tiles<2, AFFINE>(grid, s, y, f, B, n, tiles, probes, amplitude, seed, vec, partial); break;
+    case 3: rk_launch_tiles<3, AFFINE>(grid, s, y, f, B, n, tiles, probes, amplitude, seed, vec, partial); break;
+    default: rk_launch_tiles<4, AFFINE>(grid, s, y, f, B, n, tiles, probes, amplitude, seed, vec, partial); break;
+    }
+    hipLaunchKernelGGL(risk_sums_finalize_kernel, dim3(B), dim3(RK_THREADS), 0, s, partial, tiles,
+                       C * (AFFINE ? 2 + 2 * probes : 1 + probes), out);
+    return hipGetLastError() == hipSuccess ? BF_OK : BF_EHIP;
+}
+
 }  // namespace
 
 extern "C" int bf_op_risk_probe_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int probes, int amplitude,
@@ -220,32 +272,22 @@ extern "C" int bf_op_risk_probe_u8(const uint8_t* src, uint8_t* dst, int B, int 
 
 extern "C" int64_t bf_op_risk_sums_scratch_bytes(int B, int H, int W, int C, int probes)
 {
-    const int64_t n = rk_checked_elements(B, H, W, C, probes, 1);
-    if (n == 0) return BF_EINVAL;
-    return rk_tiles(n, C) * B * C * (1 + probes) * (int64_t)sizeof(double);
+    return rk_sums_scratch_bytes<false>(B, H, W, C, probes);
 }
 
 extern "C" int bf_op_risk_sums(const uint8_t* y, const float* f, int B, int H, int W, int C, int probes, int amplitude, uint64_t seed,
                                void* scratch, int64_t scratch_bytes, double* out, void* stream)
 {
-    const int64_t n = rk_checked_elements(B, H, W, C, probes, amplitude);
-    if (!y || !f || !scratch || !out || n == 0) return BF_EINVAL;
-    if (scratch_bytes < bf_op_risk_sums_scratch_bytes(B, H, W, C, probes) || ((uintptr_t)scratch | (uintptr_t)out) % 8 || (uintptr_t)f % 4)
-        return BF_EINVAL;
-    const int tiles = (int)rk_tiles(n, C);
-    const int vec = n % 4 == 0 && (uintptr_t)y % 4 == 0 && (uintptr_t)f % 16 == 0;
-    const dim3 grid((unsigned)(tiles * B));
-    hipStream_t s = (hipStream_t)stream;
-    double* partial = (double*)scratch;
-#define RK_LAUNCH(CH)                                                                                                             \
-    hipLaunchKernelGGL(risk_sums_tile_kernel<CH>, grid, dim3(RK_THREADS), 0, s, y, f, B, n, tiles, probes, amplitude, seed, vec, partial)
-    switch (C) {
-    case 1: RK_LAUNCH(1); break;
-    case 2: RK_LAUNCH(2); break;
-    case 3: RK_LAUNCH(3); break;
-    default: RK_LAUNCH(4); break;
-    }
-#undef RK_LAUNCH
-    hipLaunchKernelGGL(risk_sums_finalize_kernel, dim3(B), dim3(RK_THREADS), 0, s, partial, tiles, C * (1 + probes), out);
-    return hipGetLastError() == hipSuccess ? BF_OK : BF_EHIP;
+    return rk_sums<false>(y, f, B, H, W, C, probes, amplitude, seed, scratch, scratch_bytes, out, stream);
+}
+
+extern "C" int64_t bf_op_risk_sums_affine_scratch_bytes(int B, int H, int W, int C, int probes)
+{
+    return rk_sums_scratch_bytes<true>(B, H, W, C, probes);
+}
+
+extern "C" int bf_op_risk_sums_affine(const uint8_t* y, const float* f, int B, int H, int W, int C, int probes, int amplitude,
+                                      uint64_t seed, void* scratch, int64_t scratch_bytes, double* out, void* stream)
+{
+    return rk_sums<true>(y, f, B, H, W, C, probes, amplitude, seed, scratch, scratch_bytes, out, stream);
 }

@@ -15,6 +15,10 @@ the [(1 + K) B, H, W, C] stack.
 The estimate is only as good as its assumptions: the noise is additive, white and Gaussian, and sigma is right (by default it
 comes from `noise_statistics`, an estimator).  Saturated samples violate both and are reflected, not perturbed, by the probe; the
 clipped fraction is therefore reported next to the number (`evaluate_blind_risk`).  DESIGN.md 7.8 has the details.
+
+`estimate_risk_affine` drops the "one sigma" assumption for noise whose variance grows with the signal, var(y | x) = gain x + offset
+(camera noise): `bf_op_risk_sums_affine` adds Y = sum y and Dy_p = sum y s_p (f_p - f_0) to the sums, and the estimate is linear in
+the four.
 """
 from collections import namedtuple
 from typing import Dict, Iterable
@@ -26,6 +30,7 @@ from . import _native as N
 from .metrics import _module_device
 from .module_denoiser import DenoiserModule, GraphedDenoiserModule
 from .noise_estimate import METHODS, _check_noisy_batch, _checked_method, noise_statistics
+from .noise_level import NoiseLevelFunction, noise_level_function
 from .self_ensemble import SelfEnsembleDenoiserModule
 
 RiskEstimate = namedtuple("RiskEstimate", ["mse", "psnr", "sigma", "residual_rms", "divergence", "probe_spread", "sums"])
@@ -71,11 +76,10 @@ def risk_probe_stack_u8(image_u8: torch.Tensor, probes: int = 1, amplitude: int 
     return stack
 
 
-def risk_sums(image_u8: torch.Tensor, stack_f32: torch.Tensor, probes: int, amplitude: int, seed: int) -> torch.Tensor:
-    """bf_op_risk_sums: float64 [B, C, 1 + probes] on the device.  [..., 0] = sum over the pixels of (f_0 - y)^2, [..., p] = sum of
-    s_p (f_p - f_0), for y = image_u8 [B,H,W,C] and f = stack_f32, the float32 result [(1 + probes) B, H, W, C] for
-    risk_probe_stack_u8(image_u8, probes, amplitude, seed); the signs are regenerated, not read.  fp64 terms, fixed order."""
+def _launch_sums(affine: bool, image_u8, stack_f32, probes, amplitude, seed) -> torch.Tensor:
+    """the argument checks and the call of bf_op_risk_sums (float64 [B, C, 1 + K]) or bf_op_risk_sums_affine ([B, C, 2 + 2 K])"""
     probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
+    entry, columns = ("bf_op_risk_sums_affine", 2 + 2 * probes) if affine else ("bf_op_risk_sums", 1 + probes)
     _require_tensor(image_u8, torch.uint8, "image_u8")
     _require_tensor(stack_f32, torch.float32, "stack_f32")
     _require_device(image_u8, torch.uint8, "image_u8")
@@ -84,15 +88,21 @@ def risk_sums(image_u8: torch.Tensor, stack_f32: torch.Tensor, probes: int, ampl
         raise ValueError(f"stack_f32 must be {((1 + probes) * B, H, W, C)} on {image_u8.device} for {probes} probes of a "
                          f"{tuple(image_u8.shape)} batch, got {tuple(stack_f32.shape)} on {stack_f32.device}")
     image_u8, stack_f32 = image_u8.contiguous(), stack_f32.contiguous()
-    lib = N.lib()
-    nbytes = lib.bf_op_risk_sums_scratch_bytes(B, H, W, C, probes)
+    nbytes = getattr(N.lib(), entry + "_scratch_bytes")(B, H, W, C, probes)
     if nbytes < 0:
-        N.check(int(nbytes), None, "bf_op_risk_sums_scratch_bytes")
+        N.check(int(nbytes), None, entry + "_scratch_bytes")
     scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=image_u8.device)
-    out = torch.empty((B, C, 1 + probes), dtype=torch.float64, device=image_u8.device)
-    N.call("bf_op_risk_sums", N.ptr(image_u8), N.ptr(stack_f32), B, H, W, C, probes, amplitude, seed, N.ptr(scratch), nbytes,
-           N.ptr(out), N.stream_ptr(image_u8))
+    out = torch.empty((B, C, columns), dtype=torch.float64, device=image_u8.device)
+    N.call(entry, N.ptr(image_u8), N.ptr(stack_f32), B, H, W, C, probes, amplitude, seed, N.ptr(scratch), nbytes, N.ptr(out),
+           N.stream_ptr(image_u8))
     return out
+
+
+def risk_sums(image_u8: torch.Tensor, stack_f32: torch.Tensor, probes: int, amplitude: int, seed: int) -> torch.Tensor:
+    """bf_op_risk_sums: float64 [B, C, 1 + probes] on the device.  [..., 0] = sum over the pixels of (f_0 - y)^2, [..., p] = sum of
+    s_p (f_p - f_0), for y = image_u8 [B,H,W,C] and f = stack_f32, the float32 result [(1 + probes) B, H, W, C] for
+    risk_probe_stack_u8(image_u8, probes, amplitude, seed); the signs are regenerated, not read.  fp64 terms, fixed order."""
+    return _launch_sums(False, image_u8, stack_f32, probes, amplitude, seed)
 
 
 def risk_from_sums(sums, sigma, height: int, width: int, amplitude: int) -> RiskEstimate:
@@ -152,28 +162,27 @@ def _checked_noisy(noisy):
     return t, was_numpy
 
 
-def _checked_sigma(sigma, B: int, C: int):
+def _checked_sigma(sigma, B: int, C: int, what: str = "sigma"):
     """None, or sigma as a float64 [B, C] host-or-device tensor (a float, [C] or [B, C] was given)"""
     if sigma is None:
         return None
     try:
         s = torch.as_tensor(sigma).to(torch.float64)
     except (TypeError, ValueError, RuntimeError):
-        raise ValueError(f"sigma must be None, a float, a [C] or a [B, C] array, got {type(sigma)}") from None
+        raise ValueError(f"{what} must be None, a float, a [C] or a [B, C] array, got {type(sigma)}") from None
     if s.dim() == 0:
         s = s.reshape(1, 1).expand(B, C)
     elif tuple(s.shape) == (C,):
         s = s.reshape(1, C).expand(B, C)
     elif tuple(s.shape) != (B, C):
-        raise ValueError(f"sigma must be a float, [{C}] or [{B}, {C}] for this batch, got {tuple(s.shape)}")
+        raise ValueError(f"{what} must be a float, [{C}] or [{B}, {C}] for this batch, got {tuple(s.shape)}")
     if s.numel() and not bool((torch.isfinite(s) & (s >= 0)).all()):
-        raise ValueError("sigma must be finite and non-negative")
+        raise ValueError(f"{what} must be finite and non-negative")
     return s.contiguous()
 
 
-def _estimate(fn, noisy: torch.Tensor, sigma, method: str, probes: int, amplitude: int, seed: int) -> RiskEstimate:
-    """estimate_risk on a checked, non-empty device batch with the float form of the module"""
-    B, H, W, C = noisy.shape
+def _probed_forward(fn, noisy: torch.Tensor, probes: int, amplitude: int, seed: int) -> torch.Tensor:
+    """the float32 result of the float form of the module on the probe stack of a checked, non-empty device batch"""
     stack = risk_probe_stack_u8(noisy, probes, amplitude, seed)
     result = fn(stack)                                           # ONE call on [(1 + K) B, H, W, C]
     if isinstance(result, torch.Tensor) and result.dtype == torch.uint8:
@@ -182,7 +191,13 @@ def _estimate(fn, noisy: torch.Tensor, sigma, method: str, probes: int, amplitud
     if not isinstance(result, torch.Tensor) or result.dtype != torch.float32 or result.shape != stack.shape:
         raise ValueError(f"the module returned {getattr(result, 'dtype', type(result))} {tuple(getattr(result, 'shape', ()))} "
                          f"for a uint8 {tuple(stack.shape)} batch; float32 of the same shape is needed")
-    sums = risk_sums(noisy, result.to(noisy.device), probes, amplitude, seed)
+    return result.to(noisy.device)
+
+
+def _estimate(fn, noisy: torch.Tensor, sigma, method: str, probes: int, amplitude: int, seed: int) -> RiskEstimate:
+    """estimate_risk on a checked, non-empty device batch with the float form of the module"""
+    B, H, W, C = noisy.shape
+    sums = risk_sums(noisy, _probed_forward(fn, noisy, probes, amplitude, seed), probes, amplitude, seed)
     if sigma is None:
         sigma = noise_statistics(noisy)[:, :, 2 if method == "mad" else 1]
     return risk_from_sums(sums, sigma.to(noisy.device), H, W, amplitude)
@@ -223,6 +238,97 @@ def estimate_risk(module, noisy, sigma=None, method: str = "mad", probes: int = 
                                    "CPU execution path")
             noisy = noisy.to(_module_device(module))
         est = _estimate(fn, noisy.contiguous(), sigma, method, probes, amplitude, seed)
+    return RiskEstimate(*(v.cpu().numpy() for v in est)) if was_numpy else est
+
+
+# ---- noise whose variance is affine in the signal ------------------------------------------------
+
+def risk_sums_affine(image_u8: torch.Tensor, stack_f32: torch.Tensor, probes: int, amplitude: int, seed: int) -> torch.Tensor:
+    """bf_op_risk_sums_affine: float64 [B, C, 2 + 2 probes] on the device = (R, Y, D_1..D_K, Dy_1..Dy_K) per image and channel.  R =
+    sum (f_0 - y)^2 and D_p = sum s_p (f_p - f_0) are risk_sums' columns, with their bits; Y = sum y is an exact integer; Dy_p =
+    sum y s_p (f_p - f_0).  The arguments are risk_sums': y = image_u8 [B,H,W,C], f = stack_f32, the float32 result
+    [(1 + probes) B, H, W, C] for risk_probe_stack_u8(image_u8, probes, amplitude, seed)."""
+    return _launch_sums(True, image_u8, stack_f32, probes, amplitude, seed)
+
+
+def risk_from_affine_sums(sums, gain, offset, height: int, width: int, amplitude: int) -> RiskEstimate:
+    """The host formula for var_i = gain y_i + offset, on what bf_op_risk_sums_affine leaves.  `sums`: float64 [B, C, 2 + 2 K] =
+    (R_c, Y_c, D_1c .. D_Kc, Dy_1c .. Dy_Kc); `gain`, `offset`: float64 [B, C].  torch tensors (any device) or NumPy arrays; the
+    result is of the same kind.  With HW = height * width and a = amplitude:
+
+        mse_c = (R_c - (gain_c Y_c + offset_c HW) + 2 (gain_c mean_p Dy_pc + offset_c mean_p D_pc) / a) / HW
+        mse = mean_c mse_c                           psnr = 10 log10(255^2 / mse), +inf where mse <= 0
+        sigma_c = sqrt(gain_c Y_c / HW + offset_c), the root of the frame's mean variance
+        residual_rms = sqrt(mean_c R_c / HW)         divergence = mean_c mean_p D_pc / a / HW (not weighted)
+        probe_spread = the sample standard deviation (n - 1) over the probes of the mse each probe gives alone; NaN for K = 1"""
+    was_numpy = isinstance(sums, np.ndarray)
+    s = torch.as_tensor(sums, dtype=torch.float64)
+    g = torch.as_tensor(gain, dtype=torch.float64).to(s.device)
+    o = torch.as_tensor(offset, dtype=torch.float64).to(s.device)
+    if s.dim() != 3 or s.shape[2] < 4 or s.shape[2] % 2 or tuple(g.shape) != tuple(s.shape[:2]) or tuple(o.shape) != tuple(s.shape[:2]):
+        raise ValueError(f"sums must be [B, C, 2 + 2 K] and gain and offset [B, C], got {tuple(s.shape)}, {tuple(g.shape)} and "
+                         f"{tuple(o.shape)}")
+    C, K = s.shape[1], (s.shape[2] - 2) // 2
+    hw, a = float(int(height) * int(width)), float(amplitude)
+    fit, var = s[:, :, 0] / hw, g * s[:, :, 1] / hw + o            # [B, C]: the residual and the mean variance per sample
+    d, dy = s[:, :, 2:2 + K], s[:, :, 2 + K:]
+    wdiv_p = (g.unsqueeze(2) * dy + o.unsqueeze(2) * d) / a / hw   # [B, C, K]: sum var_i df_i/dy_i per sample, per probe
+    wdiv_c = wdiv_p.sum(dim=2) / float(K)
+    mse = (fit - var + 2.0 * wdiv_c).sum(dim=1) / float(C)
+    mse_p = (fit.unsqueeze(2) - var.unsqueeze(2) + 2.0 * wdiv_p).sum(dim=1) / float(C)                          # [B, K]
+    if K > 1:
+        spread = torch.sqrt(((mse_p - mse_p.mean(dim=1, keepdim=True)) ** 2).sum(dim=1) / float(K - 1))
+    else:
+        spread = torch.full_like(mse, float("nan"))
+    psnr = torch.where(mse > 0.0, 10.0 * torch.log10(255.0 ** 2 / mse.clamp_min(1e-300)), torch.full_like(mse, float("inf")))
+    div = d.sum(dim=2).sum(dim=1) / float(K) / a / hw / float(C)
+    est = RiskEstimate(mse, psnr, torch.sqrt(var.clamp_min(0.0)), torch.sqrt(fit.sum(dim=1) / float(C)), div, spread, s)
+    return RiskEstimate(*(v.cpu().numpy() for v in est)) if was_numpy else est
+
+
+def estimate_risk_affine(module, noisy, nlf=None, probes: int = 1, amplitude: int = 1, seed: int = 0) -> RiskEstimate:
+    """estimate_risk for noise whose variance grows with the signal, var(y_i | x_i) = gain x_i + offset (shot noise plus read noise):
+    for independent Gaussian noise of variances v_i,  E |f(y) - x|^2 = E[ |f(y) - y|^2 - sum v_i + 2 sum v_i df_i/dy_i ], and with
+    the plug-in v_i = gain y_i + offset everything is linear in the sums of bf_op_risk_sums_affine (risk_from_affine_sums has the
+    formula).  Returns the RiskEstimate of estimate_risk; its `sigma` [B,C] is sqrt(gain mean(y) + offset) and its `sums` are
+    [B,C,2+2 probes].
+
+    `nlf`: a NoiseLevelFunction (noise_level.noise_level_function), a (gain, offset) pair -- each a float, [C] or [B,C], in grey
+    levels and grey levels squared -- or None for noise_level_function(noisy) (needs H, W >= 3).  `module`, `noisy`, `probes`,
+    `amplitude` and `seed` as estimate_risk; the same probe stack and ONE module call.
+
+    What is approximate: the plug-in weighs the divergence with v(y_i) where the identity has v(x_i).  Since E[(y_i - x_i) g(y)] =
+    v_i E dg/dy_i, this adds 2 gain v_i E d2f_i/dy_i^2 per sample, a second-order term: the estimate is unbiased for every linear f
+    and close for a smooth one; the noise is taken as Gaussian (shot noise is Poisson: good above a few tens of electrons) and
+    clipping at 0 and 255 is not modelled.  DESIGN.md 7.10 has the measured sizes."""
+    probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
+    fn = _float_callable(module)
+    noisy, was_numpy = _checked_noisy(noisy)
+    B, H, W, C = noisy.shape
+    if nlf is not None:
+        pair = (nlf.gain, nlf.offset) if isinstance(nlf, NoiseLevelFunction) else nlf
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2 or pair[0] is None or pair[1] is None:
+            raise ValueError("nlf must be None, a NoiseLevelFunction or a (gain, offset) pair")
+        try:                                                     # Python floats as float64, not as torch's default float32
+            pair = [v if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64) for v in pair]
+        except (TypeError, ValueError):
+            raise ValueError("gain and offset must each be a float, a [C] or a [B, C] array") from None
+        gain, offset = _checked_sigma(pair[0], B, C, "gain"), _checked_sigma(pair[1], B, C, "offset")
+    if B == 0:
+        empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=noisy.device)
+        est = RiskEstimate(empty(0), empty(0), empty(0, C), empty(0), empty(0), empty(0), empty(0, C, 2 + 2 * probes))
+    else:
+        if was_numpy or not noisy.is_cuda:
+            if not was_numpy:
+                raise RuntimeError("noisy must live on the GPU (or be a NumPy array, which is uploaded): the risk kernels have no "
+                                   "CPU execution path")
+            noisy = noisy.to(_module_device(module))
+        noisy = noisy.contiguous()
+        if nlf is None:
+            fitted = noise_level_function(noisy)
+            gain, offset = fitted.gain, fitted.offset
+        sums = risk_sums_affine(noisy, _probed_forward(fn, noisy, probes, amplitude, seed), probes, amplitude, seed)
+        est = risk_from_affine_sums(sums, gain.to(noisy.device), offset.to(noisy.device), H, W, amplitude)
     return RiskEstimate(*(v.cpu().numpy() for v in est)) if was_numpy else est
 
 

@@ -247,6 +247,32 @@ int64_t bf_noise_estimate_scratch_bytes(int batch, int height, int width, int ch
 int bf_noise_estimate(const void* img, int dtype, int batch, int height, int width, int channels, void* scratch,
                       int64_t scratch_bytes, double* out, void* stream);
 
+/* Noise level statistics of one uint8 NHWC batch in one pass (csrc/noise_level.hip): the MAD estimator above conditioned on the
+ * local intensity, for noise whose variance grows with the signal (var(y | x) = a x + b).  Per complete 2x2 cell and channel:
+ * q = |x00 - x01 - x10 + x11| (0..510) and s = x00 + x01 + x10 + x11 (0..1020); a cell with a sample equal to 0 or 255 is excluded
+ * and only counted; every other cell belongs to level l = s >> 6 (16 levels, each 16 grey levels of cell mean wide).
+ *   out_levels   = double[batch][channels][16][3] = (n, the sum of s, sigma_l) per level: n cells, sigma_l = med / 2 / 0.6745 with
+ *                  med the grouped-data median of the level's 511-bin histogram of q, by the rule of bf_noise_estimate (0 for an
+ *                  empty level or when every cell is zero)
+ *   out_excluded = double[batch][channels], the number of excluded cells
+ * Everything is a 64-bit integer sum, exact in any order: repeated calls return the same bits, and an image inside a batch the
+ * bits of that image alone.  height and width >= 3, channels in 1..4.  `scratch`: bf_noise_level_scratch_bytes bytes, 8-byte
+ * aligned, zeroed by the call on `stream`; nothing is allocated and nothing synchronises.  BF_EINVAL for NULL, a bad shape, or
+ * short or misaligned scratch. */
+int64_t bf_noise_level_scratch_bytes(int batch, int height, int width, int channels);
+int bf_noise_level(const uint8_t* img, int batch, int height, int width, int channels, void* scratch, int64_t scratch_bytes,
+                   double* out_levels, double* out_excluded, void* stream);
+
+/* Signal-dependent (Poisson-Gaussian) camera noise on a uint8 NHWC batch (csrc/augment.hip), channels in 1..4, H W C < 2^31 - 4096:
+ *   dst = clip(rint(src + sqrt(gain[c] src + read_sigma[c]^2) z), 0, 255), in float32, z an untruncated standard normal:
+ *   z = sqrt(-2 ln u1) cos(2 pi u2), u1 = ((r[0] >> 8) + 1) / 2^24, u2 = (r[1] >> 8) / 2^24, r = philox4x32_10(counter = (lo32 e,
+ *   hi32 e, 0, 3), key = (lo32 seed, hi32 seed)), e = (h W + w) C + c inside the image: an image gets the same bits alone or inside
+ *   a batch.  `gain` and `read_sigma` are HOST arrays of `channels` floats, read by the call and passed to the kernel by value.
+ * dst may be src.  One launch, no allocation, no synchronisation.  BF_EINVAL for NULL, a bad shape, or a gain or read_sigma that is
+ * negative or not finite. */
+int bf_op_camera_noise_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, const float* gain, const float* read_sigma,
+                          uint64_t seed, void* stream);
+
 /* ---- unet_laplacian backbone operators (BASELINE.json configs[4]) ------------------------------
  * What bfcnn/backbone_unet_laplacian.py:281-606 builds from keras layers, as fp32 NHWC device operators; the host
  * (blind_image_denoising_amd/unet_laplacian.py) chains them as the reference builder chains its layers.
@@ -659,6 +685,15 @@ int bf_op_risk_probe_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, i
 int64_t bf_op_risk_sums_scratch_bytes(int B, int H, int W, int C, int probes);
 int bf_op_risk_sums(const uint8_t* y, const float* f, int B, int H, int W, int C, int probes, int amplitude, uint64_t seed,
                     void* scratch, int64_t scratch_bytes, double* out, void* stream);
+
+/* bf_op_risk_sums for noise whose variance is affine in the signal, var_i = a y_i + b (plugged in at the noisy value):
+ * E |f(y) - x|^2 = E[ |f(y) - y|^2 - sum var_i + 2 sum var_i df_i/dy_i ] is linear in four kinds of sums per image and channel.
+ *   out = device double[B][C][2 + 2 probes] = (R, Y, D_1..D_K, Dy_1..Dy_K):  R and D_p as bf_op_risk_sums and with its bits,
+ *   Y = sum y (an exact integer),  Dy_p = sum of y s_p (f_p - f_0).
+ * The same probe stack, signs, unit ownership and fixed-order reduction; scratch: bf_op_risk_sums_affine_scratch_bytes bytes. */
+int64_t bf_op_risk_sums_affine_scratch_bytes(int B, int H, int W, int C, int probes);
+int bf_op_risk_sums_affine(const uint8_t* y, const float* f, int B, int H, int W, int C, int probes, int amplitude, uint64_t seed,
+                           void* scratch, int64_t scratch_bytes, double* out, void* stream);
 
 /* ---- training on noisy images alone: Neighbor2Neighbor pairs (Huang et al., CVPR 2021; blind_image_denoising_amd/neighbor.py is
  * the host side; csrc/neighbor.hip).  From a noisy batch y [B,H,W,C] (uint8 when y_is_u8 != 0, else float32; H, W even and >= 2,
