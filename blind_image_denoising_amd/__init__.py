@@ -38,6 +38,8 @@ from .noise_level import NoiseLevelFunction, noise_level_statistics, noise_level
 from . import risk
 from .risk import RiskEstimate, risk_probe_stack_u8, risk_sums, estimate_risk, evaluate_blind_risk, format_risk_report
 from .risk import risk_sums_affine, risk_from_affine_sums, estimate_risk_affine
+from . import vst
+from .vst import StabilisedDenoiserModule, stabilise_u8, unstabilise, evaluate_camera, format_camera_report
 from . import neighbor
 from .neighbor import neighbor_pairs, NeighborPairs, RiskValidator, parse_self_supervised_config
 from . import regularizers
@@ -81,14 +83,24 @@ if pretrained_dir.is_dir():
         }
 
 
-def load_model(model_path: str, device=None, self_ensemble=None):
+def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None):
     """bfcnn/__init__.py:81-97: a registry name, a model directory (pipeline.json + weights.npz written by
     `save_model`), or a `.keras` archive of a trained unet_laplacian hydra / the directory holding `model_hydra.keras`
     (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]: a
     DenoiserModule, or with `self_ensemble` = "d4", "flips" or a sequence of transform numbers 0..7 that module wrapped in a
-    SelfEnsembleDenoiserModule (the mean over the flips and rotations of the image; self_ensemble.py)."""
+    SelfEnsembleDenoiserModule (the mean over the flips and rotations of the image; self_ensemble.py).  `stabilise` = True or a
+    (gain, offset) pair wraps the result (after any self-ensemble wrapper) in a StabilisedDenoiserModule for camera noise whose
+    variance is gain x + offset: True fits the pair per frame, a pair fixes it (vst.py)."""
+    if stabilise is not None and not isinstance(stabilise, (bool, tuple, list)):
+        raise ValueError(f"stabilise must be None, a bool or a (gain, offset) pair, got {stabilise!r}")
+    if stabilise is not None and not isinstance(stabilise, bool):
+        vst._checked_noise_level(stabilise)                      # a bad pair is refused before anything is loaded
     module = _load_module(model_path, device)
-    return module if self_ensemble is None else SelfEnsembleDenoiserModule(module, transforms=self_ensemble)
+    if self_ensemble is not None:
+        module = SelfEnsembleDenoiserModule(module, transforms=self_ensemble)
+    if stabilise is None or stabilise is False:
+        return module
+    return StabilisedDenoiserModule(module, None if stabilise is True else stabilise)
 
 
 def _load_module(model_path: str, device=None) -> DenoiserModule:

@@ -77,6 +77,8 @@ SIGNATURES = {
     "bf_noise_level_scratch_bytes": (_I64, [_I, _I, _I, _I]),
     "bf_noise_level": (_I, [_P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
     "bf_op_camera_noise_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, C.c_uint64, _P]),
+    "bf_op_vst_forward_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "bf_op_vst_inverse": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
     "bf_op_pack_pointwise": (_I, [_P, _P, _I, _I, _P]),
     "bf_op_pointwise": (_I, [_P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _F, _P]),
     "bf_op_pointwise_ex": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _F, _I, _P]),

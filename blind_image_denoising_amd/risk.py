@@ -32,6 +32,7 @@ from .module_denoiser import DenoiserModule, GraphedDenoiserModule
 from .noise_estimate import METHODS, _check_noisy_batch, _checked_method, noise_statistics
 from .noise_level import NoiseLevelFunction, noise_level_function
 from .self_ensemble import SelfEnsembleDenoiserModule
+from .vst import StabilisedDenoiserModule
 
 RiskEstimate = namedtuple("RiskEstimate", ["mse", "psnr", "sigma", "residual_rms", "divergence", "probe_spread", "sums"])
 
@@ -139,6 +140,9 @@ def _float_callable(module):
     """the float32 form of `module`: uint8 [B,H,W,C] device tensor -> float32 of the same shape, not rounded"""
     if isinstance(module, GraphedDenoiserModule):
         module = module._module                                  # the wrapped module, called directly
+    if isinstance(module, StabilisedDenoiserModule):             # the whole pipeline: transform, module, inverse, not rounded
+        return StabilisedDenoiserModule(module._module, module.noise_level, module.inverse, cast_to_uint8=False,
+                                        min_cells=module.min_cells)
     if isinstance(module, SelfEnsembleDenoiserModule):
         return SelfEnsembleDenoiserModule(module._module, module.transforms, cast_to_uint8=False)
     if isinstance(module, DenoiserModule):
@@ -146,8 +150,8 @@ def _float_callable(module):
         inner._deferred = module._deferred                       # one record of pending status words: module.check_status() sees this call
         return inner
     if not callable(module):
-        raise ValueError("module must be a DenoiserModule, GraphedDenoiserModule, SelfEnsembleDenoiserModule or a callable "
-                         "uint8 [B,H,W,C] -> float32 [B,H,W,C]")
+        raise ValueError("module must be a DenoiserModule, GraphedDenoiserModule, SelfEnsembleDenoiserModule, "
+                         "StabilisedDenoiserModule or a callable uint8 [B,H,W,C] -> float32 [B,H,W,C]")
     return module
 
 
@@ -296,6 +300,11 @@ def estimate_risk_affine(module, noisy, nlf=None, probes: int = 1, amplitude: in
     `nlf`: a NoiseLevelFunction (noise_level.noise_level_function), a (gain, offset) pair -- each a float, [C] or [B,C], in grey
     levels and grey levels squared -- or None for noise_level_function(noisy) (needs H, W >= 3).  `module`, `noisy`, `probes`,
     `amplitude` and `seed` as estimate_risk; the same probe stack and ONE module call.
+
+    A StabilisedDenoiserModule (vst.py) is scored as the whole pipeline -- transform, module, inverse -- in its cast_to_uint8=False
+    form.  With its noise_level=None every member of the probe stack is fitted on its own: the fit is part of the function being
+    scored, and its reaction to the probe enters the divergence.  A fixed noise level of shape [B,C] does not match the
+    [(1 + probes) B] stack (ValueError): give [C] or floats.
 
     What is approximate: the plug-in weighs the divergence with v(y_i) where the identity has v(x_i).  Since E[(y_i - x_i) g(y)] =
     v_i E dg/dy_i, this adds 2 gain v_i E d2f_i/dy_i^2 per sample, a second-order term: the estimate is unbiased for every linear f

@@ -1,0 +1,287 @@
+"""
+Denoise camera noise with a Gaussian denoiser: variance stabilisation around the call.
+
+Every network here is trained on additive Gaussian noise of one sigma per frame; camera noise has var(y | x) = gain x + offset,
+a sigma that changes by a factor of several between the shadows and the highlights of one frame.  The standard remedy needs no
+retraining: the generalised Anscombe transform with the frame's (gain, offset) makes the noise Gaussian of one standard deviation
+everywhere, the denoiser runs on that, and the exact unbiased inverse of Makitalo & Foi (IEEE TIP 2013, closed form) returns to
+grey levels without the bias the algebraic inverse has.  Two kernels of csrc/vst.hip carry everything that is not the denoiser:
+`bf_op_vst_forward_u8` (uint8 -> uint8 through a table per image, built in fp64; 0 -> 0, 255 -> 255, the identity for gain 0) and
+`bf_op_vst_inverse` (float32 -> float32 or uint8).  Both read (gain, offset) as fp64 [B,C] DEVICE tensors, which is what
+`noise_level_function` leaves there: the fit never comes to the host.  DESIGN.md 7.11 has the formulas and what was measured.
+There is no CPU execution path.
+"""
+from typing import Dict, Iterable
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .constants import DENOISER_STR
+from .noise_level import NoiseLevelFunction, camera_noise, noise_level_function
+
+GAIN_MAX, OFFSET_MAX = 64.0, 65025.0
+INVERSES = ("exact", "algebraic")
+_NO_GPU = "must live on the GPU: the stabilisation kernels have no CPU execution path"
+
+
+def _checked_inverse(inverse) -> str:
+    if inverse not in INVERSES:
+        raise ValueError(f"inverse must be one of {list(INVERSES)}, got {inverse!r}")
+    return inverse
+
+
+def _checked_noise_level(noise_level):
+    """(gain, offset) of a NoiseLevelFunction or a (gain, offset) pair.  Device tensors are passed on as they are (the kernels
+    sanitise what they read); everything else is host-given: float64 NumPy arrays of at most two dimensions, finite, 0 <= gain <=
+    64, 0 <= offset <= 65025, else ValueError."""
+    pair = (noise_level.gain, noise_level.offset) if isinstance(noise_level, NoiseLevelFunction) else noise_level
+    if not isinstance(pair, (tuple, list)) or len(pair) != 2 or pair[0] is None or pair[1] is None:
+        raise ValueError("noise_level must be a NoiseLevelFunction or a (gain, offset) pair")
+    out = []
+    for value, what, top in ((pair[0], "gain", GAIN_MAX), (pair[1], "offset", OFFSET_MAX)):
+        if isinstance(value, torch.Tensor) and value.is_cuda:
+            if value.dim() > 2:
+                raise ValueError(f"{what} must be a float, [C] or [B,C], got shape {tuple(value.shape)}")
+            out.append(value)
+            continue
+        try:
+            a = np.asarray(value.detach().numpy() if isinstance(value, torch.Tensor) else value, dtype=np.float64)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"{what} must be a float, a [C] or a [B,C] array, got {type(value)}") from None
+        if a.ndim > 2:
+            raise ValueError(f"{what} must be a float, [C] or [B,C], got shape {a.shape}")
+        if not np.all(np.isfinite(a)) or np.any(a < 0) or np.any(a > top):
+            raise ValueError(f"{what} must be finite and in 0..{top:g}, got {a.tolist()}")
+        out.append(a)
+    return out[0], out[1]
+
+
+def _require_images(t, dtype, what: str):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 4:
+        raise ValueError(f"{what} must be a {dtype} tensor of shape [B,H,W,C], got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    B, H, W, C = t.shape
+    if not 1 <= C <= 4 or B < 1 or H < 1 or W < 1:
+        raise ValueError(f"{what} must be a non-empty [B,H,W,C] batch with 1..4 channels, got {tuple(t.shape)}")
+
+
+def _launch_arguments(images, dtype, what: str, noise_level):
+    """the argument checks shared by both directions: (contiguous images, gain [B,C], offset [B,C]) on the images' device"""
+    _require_images(images, dtype, what)
+    pair = _checked_noise_level(noise_level)                    # host-given values are refused before the GPU is touched
+    B, _, _, C = images.shape
+    for value, name in zip(pair, ("gain", "offset")):
+        shape = tuple(value.shape)
+        if shape not in ((), (C,), (B, C)):
+            raise ValueError(f"{name} must be a float, [{C}] or [{B}, {C}] for this batch, got {shape}")
+    if not images.is_cuda:
+        raise RuntimeError(f"{what} {_NO_GPU}")
+    gain, offset = (torch.as_tensor(v).to(device=images.device, dtype=torch.float64).expand(B, C).contiguous() for v in pair)
+    return images.contiguous(), gain, offset
+
+
+def stabilise_u8(images_u8: torch.Tensor, noise_level) -> torch.Tensor:
+    """bf_op_vst_forward_u8 on a uint8 device tensor [B,H,W,C] (C in 1..4): uint8 of the same shape, v = rint(s u(y)) with u(y) =
+    2 y / (sqrt(a y + c) + rc), c = 3/8 a^2 + o, rc = sqrt(c), s = 255 / u(255), per image and channel.  The noise of variance
+    a x + o has the standard deviation s everywhere in v; 0 stays 0, 255 stays 255, and a = 0 gives v = y.
+
+    `noise_level`: a NoiseLevelFunction (noise_level_function's, device tensors or NumPy) or a (gain, offset) pair, each a float,
+    [C] or [B,C].  Host-given values must be finite with 0 <= gain <= 64 and 0 <= offset <= 65025 (ValueError before the GPU is
+    touched) and are uploaded as float64; device tensors are read as they are and sanitised by the kernel (gain not finite or not
+    positive: 0, capped at 64; offset clamped to [1/12, 65025], 1/12 when not finite -- the variance rounding to grey levels gives
+    any uint8 image)."""
+    images_u8, gain, offset = _launch_arguments(images_u8, torch.uint8, "images_u8", noise_level)
+    B, H, W, C = images_u8.shape
+    out = torch.empty_like(images_u8)
+    N.call("bf_op_vst_forward_u8", N.ptr(images_u8), N.ptr(out), B, H, W, C, N.ptr(gain), N.ptr(offset), N.stream_ptr(images_u8))
+    return out
+
+
+def unstabilise(stabilised_f32: torch.Tensor, noise_level, inverse: str = "exact", cast_to_uint8: bool = True) -> torch.Tensor:
+    """bf_op_vst_inverse on a float32 device tensor [B,H,W,C] in the stabilised domain (what a denoiser returns for
+    stabilise_u8's output): with w clamped to [0, 255] and u = w / s,
+
+        algebraic   x = rc u + a u^2 / 4
+        exact       x = algebraic + a / 4 + a (K1 d - K2 d^2 + K3 d^3),   d = a / (a u + 2 rc)
+
+    K1 = sqrt(3/2) / 4, K2 = 11/8, K3 = 5 sqrt(3/2) / 8: the closed form of the exact unbiased inverse of Makitalo & Foi (2013)
+    with the terms that diverge as a -> 0 cancelled.  x is clipped to [0, 255]: float32, or uint8 rounded half to even.
+    `noise_level` as stabilise_u8 (the same one)."""
+    _checked_inverse(inverse)
+    stabilised_f32, gain, offset = _launch_arguments(stabilised_f32, torch.float32, "stabilised_f32", noise_level)
+    B, H, W, C = stabilised_f32.shape
+    out = torch.empty((B, H, W, C), dtype=torch.uint8 if cast_to_uint8 else torch.float32, device=stabilised_f32.device)
+    N.call("bf_op_vst_inverse", N.ptr(stabilised_f32), N.ptr(out), B, H, W, C, N.ptr(gain), N.ptr(offset), int(inverse == "exact"),
+           int(bool(cast_to_uint8)), N.stream_ptr(stabilised_f32))
+    return out
+
+
+class StabilisedDenoiserModule:
+    """A denoiser run between the variance-stabilising transform and its inverse: uint8 [B,H,W,C] -> uint8 [B,H,W,C] (float32,
+    not rounded, with cast_to_uint8=False).  `module`: a DenoiserModule, a SelfEnsembleDenoiserModule, or any callable that maps a
+    uint8 device tensor [N,H,W,C] to float32 of the same shape; its float32 form is what runs (risk._float_callable).
+
+    A call is: the argument checks and host-or-device input handling of DenoiserModule; with `noise_level=None` the fit
+    noise_level_function(image, min_cells), per image of the batch given, on the device (needs H, W >= 3); stabilise_u8; the float
+    module; unstabilise(inverse).  A fixed `noise_level` (a NoiseLevelFunction or a (gain, offset) pair, as stabilise_u8 takes it)
+    of shape [B,C] must match the batch, else ValueError.  `last_noise_level` holds the fit of the last call (the
+    NoiseLevelFunction, device tensors), or the fixed pair as it was given.
+
+    The f16-range status of the inner calls is kept where the wrapped module keeps its own: `check_status` is the wrapped
+    module's, and a host-array call that hits the range switches the model to the exact-fp32 kernels and repeats itself, as a
+    DenoiserModule call does.  With gain 0 the forward map is the identity and the inverse x = rc (w / s) = w up to two float32
+    roundings: the wrapper then returns what the module returns to within those."""
+
+    def __init__(self, module, noise_level=None, inverse: str = "exact", cast_to_uint8: bool = True, min_cells: int = 64):
+        from .module_denoiser import DenoiserModule
+        from .risk import _float_callable
+        if isinstance(module, StabilisedDenoiserModule):
+            raise ValueError("module is already stabilised")
+        self._float = _float_callable(module)                    # ValueError for what is not callable
+        self._module, self._inverse, self._cast_to_uint8 = module, _checked_inverse(inverse), bool(cast_to_uint8)
+        if isinstance(min_cells, bool) or not isinstance(min_cells, (int, np.integer)) or min_cells < 1:
+            raise ValueError(f"min_cells must be a positive int, got {min_cells!r}")
+        self._min_cells = int(min_cells)
+        self._noise_level = None if noise_level is None else _checked_noise_level(noise_level)
+        base = module if isinstance(module, DenoiserModule) else getattr(module, "_module", None)
+        self._base = base if isinstance(base, DenoiserModule) else None      # whose argument checks and empty output a call uses
+        self.name = getattr(module, "name", DENOISER_STR)
+        self.last_noise_level = None
+
+    @property
+    def model_hydra(self):
+        return getattr(self._module, "model_hydra", None)
+
+    @property
+    def noise_level(self):
+        return self._noise_level
+
+    @property
+    def inverse(self) -> str:
+        return self._inverse
+
+    @property
+    def min_cells(self) -> int:
+        return self._min_cells
+
+    def check_status(self, wait: bool = True) -> bool:
+        return self._module.check_status(wait) if hasattr(self._module, "check_status") else True
+
+    def _checked_input(self, image):
+        if self._base is not None:
+            return self._base._checked_input(image)
+        was_numpy = isinstance(image, np.ndarray)
+        if was_numpy:
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        if not isinstance(image, torch.Tensor) or image.dtype != torch.uint8 or image.dim() != 4:
+            raise ValueError(f"input must be a uint8 tensor or array of shape [B,H,W,C], got "
+                             f"{getattr(image, 'dtype', type(image))} {tuple(getattr(image, 'shape', ()))}")
+        if not 1 <= image.shape[3] <= 4:
+            raise ValueError(f"expected 1..4 channels, got {image.shape[3]}")
+        return image, was_numpy
+
+    def __call__(self, image):
+        image, was_numpy = self._checked_input(image)
+        B, H, W, C = image.shape
+        if self._noise_level is not None:
+            for value, what in zip(self._noise_level, ("gain", "offset")):
+                if tuple(value.shape) not in ((), (C,), (B, C)):
+                    raise ValueError(f"{what} must be a float, [{C}] or [{B}, {C}] for this batch, got {tuple(value.shape)}")
+        if B == 0:
+            if self._base is not None:
+                return self._base._empty_output(image, was_numpy)
+            return image.numpy() if was_numpy else image
+        hydra = self.model_hydra
+        if hydra is not None:
+            hydra._require_gpu()
+            image = image.to(hydra.device)
+        elif was_numpy:
+            if not torch.cuda.is_available():
+                raise RuntimeError(f"image {_NO_GPU}")
+            image = image.cuda()
+        image = image.contiguous()
+        if self._noise_level is None:
+            level = noise_level_function(image, self._min_cells)
+            self.last_noise_level = level
+        else:
+            level = self.last_noise_level = self._noise_level
+        result = self._float(stabilise_u8(image, level))
+        if was_numpy and not self.check_status(wait=True):
+            # host arrays are handed back and an activation left the f16 range: the model now runs the exact-fp32 kernels
+            # (check_status switched it); repeat the call
+            return self(image.cpu().numpy())
+        if not isinstance(result, torch.Tensor) or result.dtype != torch.float32 or result.shape != image.shape:
+            raise ValueError(f"the module returned {getattr(result, 'dtype', type(result))} {tuple(getattr(result, 'shape', ()))} "
+                             f"for a uint8 {tuple(image.shape)} batch; float32 of the same shape is needed")
+        out = unstabilise(result.to(image.device), level, self._inverse, self._cast_to_uint8)
+        return out.cpu().numpy() if was_numpy else out
+
+
+# ---- evaluation on synthetic camera noise --------------------------------------------------------
+
+_ARMS = ("noisy", "direct", "stabilised_known", "stabilised_fitted")
+_METRICS = ("psnr", "ssim", "mae")
+
+
+def evaluate_camera(module, clean_batches: Iterable, gain: float, read_sigma: float, seed: int = 0) -> Dict:
+    """What stabilisation is worth for `module` on camera noise of a known (gain, read_sigma): every clean uint8 batch (host or
+    device, H and W >= 11 for the SSIM window) gets camera_noise(clean, gain, read_sigma, seed + k), and PSNR, SSIM and MAE
+    (metrics.image_metrics) against the clean frames are taken of four things: the noisy frame, the module applied directly, the
+    module stabilised with the known (gain, read_sigma^2 + 1/12), and the module stabilised with the frame's own fit.  `module`: a
+    DenoiserModule or SelfEnsembleDenoiserModule (uint8 -> uint8).  Returns {"gain", "read_sigma", "images", "batches": [one dict per
+    batch], "aggregate"}: per entry psnr_*, ssim_*, mae_* for the four arms (means over the images) and fitted_gain /
+    fitted_offset (means over images and channels).  Nothing is asserted; the module's deferred f16-range status is checked once
+    at the end."""
+    from .metrics import _check_clean_batch, _module_device, image_metrics
+    for value, what in ((gain, "gain"), (read_sigma, "read_sigma")):
+        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not np.isfinite(value) \
+                or value < 0:
+            raise ValueError(f"{what} must be a non-negative float, got {value!r}")
+    known = (float(gain), float(read_sigma) ** 2 + 1.0 / 12.0)
+    arms = {"direct": module,
+            "stabilised_known": StabilisedDenoiserModule(module, known),
+            "stabilised_fitted": StabilisedDenoiserModule(module, None)}
+    batches = [_check_clean_batch(b) for b in clean_batches]
+    if not batches:
+        raise ValueError("no clean batches to evaluate on")
+    dev = _module_device(module)
+    per_batch = []                                               # one [14, B] device tensor per batch
+    for k, clean in enumerate(batches):
+        clean = clean.to(dev).contiguous()
+        noisy = camera_noise(clean, float(gain), float(read_sigma), (int(seed) + k) % 2 ** 64)
+        rows = list(image_metrics(clean, noisy)[:3])
+        for name in _ARMS[1:]:
+            denoised = arms[name](noisy)
+            if not isinstance(denoised, torch.Tensor) or denoised.dtype != torch.uint8 or denoised.shape != clean.shape:
+                raise ValueError(f"the module returned {getattr(denoised, 'dtype', type(denoised))} "
+                                 f"{tuple(getattr(denoised, 'shape', ()))} for a uint8 {tuple(clean.shape)} batch")
+            rows += list(image_metrics(clean, denoised)[:3])
+        fit = arms["stabilised_fitted"].last_noise_level
+        rows += [fit.gain.mean(dim=1), fit.offset.mean(dim=1)]
+        per_batch.append(torch.stack(rows))
+    if hasattr(module, "check_status"):
+        module.check_status()                                    # an overflow of the split-f16 kernels is not averaged into a number
+    keys = [f"{m}_{arm}" for arm in _ARMS for m in _METRICS] + ["fitted_gain", "fitted_offset"]
+    host = [p.cpu().numpy() for p in per_batch]
+    rows = [{"shape": [int(v) for v in b.shape], "images": int(h.shape[1]), **{key: float(h[i].mean()) for i, key in enumerate(keys)}}
+            for b, h in zip(batches, host)]
+    every = np.concatenate(host, axis=1)
+    aggregate = {"images": int(every.shape[1]), **{key: float(every[i].mean()) for i, key in enumerate(keys)}}
+    return {"gain": float(gain), "read_sigma": float(read_sigma), "images": aggregate["images"], "batches": rows,
+            "aggregate": aggregate}
+
+
+def format_camera_report(report: Dict) -> str:
+    """the table tools/evaluate_camera.py prints"""
+    lines = [f"camera noise: gain {report['gain']:g}, read sigma {report['read_sigma']:g}; fitted gain "
+             f"{report['aggregate']['fitted_gain']:.3f}, offset {report['aggregate']['fitted_offset']:.3f}",
+             "batch            shape  images  arm                    psnr      ssim       mae"]
+
+    def block(name, shape, r):
+        return [f"{name:>5}  {shape:>15}  {r['images']:6d}  {arm:<18} {r['psnr_' + arm]:8.3f}  {r['ssim_' + arm]:8.5f}  {r['mae_' + arm]:8.3f}"
+                for arm in _ARMS]
+    for i, r in enumerate(report["batches"]):
+        lines += block(str(i), "x".join(map(str, r["shape"])), r)
+    lines += block("all", "", report["aggregate"])
+    return "\n".join(lines)

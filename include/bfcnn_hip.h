@@ -273,6 +273,26 @@ int bf_noise_level(const uint8_t* img, int batch, int height, int width, int cha
 int bf_op_camera_noise_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, const float* gain, const float* read_sigma,
                           uint64_t seed, void* stream);
 
+/* Variance stabilisation of a uint8 NHWC batch whose noise variance is gain x + offset, and the way back (csrc/vst.hip; DESIGN.md
+ * 7.11).  `gain` and `offset` are DEVICE arrays double[B][C] (what the fit of bf_noise_level leaves on the device), 8-byte aligned;
+ * per image and channel, sanitised where they are used: a = gain finite and > 0 ? min(gain, 64) : 0, o = offset finite ?
+ * clamp(offset, 1/12, 65025) : 1/12, c = 3/8 a^2 + o, rc = sqrt(c).
+ *   forward: dst = rint(s u(src)), u(y) = 2 y / (sqrt(a y + c) + rc) (the generalised Anscombe transform minus its value at 0),
+ *     s = 255 / u(255), in fp64 through a table per image: 0 -> 0, 255 -> 255, noise of standard deviation s everywhere, the
+ *     identity for a = 0.  dst may be src.
+ *   inverse: src = float32 in the stabilised domain, clamped to [0, 255]; u = src / s, x = rc u + a u^2 / 4, and with exact != 0
+ *     the exact unbiased inverse of Makitalo & Foi (2013): x += a / 4 + a (K1 d - K2 d^2 + K3 d^3), d = a / (a u + 2 rc), K1 =
+ *     sqrt(3/2) / 4, K2 = 11/8, K3 = 5 sqrt(3/2) / 8.  float32 arithmetic (the reciprocal to 1 ulp) on constants folded in fp64,
+ *     within 1e-3 of the fp64 value (measured: 5.5e-5); dst = x clipped to [0, 255]
+ *     as float32, or with cast_to_uint8 != 0 rounded half to even to uint8.  A float32 dst may be src.
+ * Flat per image, channel = element index mod C: an image gets the same bits alone or inside a batch.  C in 1..4, B <= 65535,
+ * H W C < 2^31 - 4096.  One launch, no atomics, no allocation, no synchronisation.  BF_EINVAL for NULL, a misaligned pointer
+ * (gain, offset: 8 bytes; float32 images: 4 bytes), a bad shape, or a uint8 dst on top of its float32 src. */
+int bf_op_vst_forward_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, const double* gain, const double* offset,
+                         void* stream);
+int bf_op_vst_inverse(const float* src, void* dst, int B, int H, int W, int C, const double* gain, const double* offset, int exact,
+                      int cast_to_uint8, void* stream);
+
 /* ---- unet_laplacian backbone operators (BASELINE.json configs[4]) ------------------------------
  * What bfcnn/backbone_unet_laplacian.py:281-606 builds from keras layers, as fp32 NHWC device operators; the host
  * (blind_image_denoising_amd/unet_laplacian.py) chains them as the reference builder chains its layers.
