@@ -309,6 +309,15 @@ def call(fn_name: str, *args):
     check(getattr(lib(), fn_name)(*args), None, fn_name)
 
 
+def scratch(entry: str, device, *dims):
+    """(the float64 scratch tensor `entry` needs for `dims` on `device`, its size in bytes): what `entry`_scratch_bytes says"""
+    import torch
+    nbytes = getattr(lib(), entry + "_scratch_bytes")(*dims)
+    if nbytes < 0:
+        check(int(nbytes), None, entry + "_scratch_bytes")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device), nbytes
+
+
 def ptr(t):
     """Device (or host) address of a torch tensor / None."""
     if t is None:

@@ -19,45 +19,33 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _native as N
 from .custom_logger import logger
+from .module_denoiser import DenoiserModule
 
 ImageMetrics = namedtuple("ImageMetrics", ["psnr", "ssim", "mae", "mse"])
 
 DEFAULT_NOISE_STD = (10, 15, 20, 25, 30)                 # tests/bfcnn/test_pretrained.py:30
 DEFAULT_TRAIN_NOISE_STD = (0, 20, 40, 60, 80)            # bfcnn/train_loop.py:507-509
 _DTYPES = {torch.uint8: N.BF_DTYPE_U8, torch.float32: N.BF_DTYPE_F32}
+_FEATURE = "image_metrics"
+
+
+def _checked_window(filter_size) -> int:
+    if int(filter_size) < 3 or int(filter_size) > 11 or int(filter_size) % 2 == 0:
+        raise ValueError(f"filter_size must be odd and in 3..11, got {filter_size}")
+    return int(filter_size)
 
 
 def _as_tensor_pair(a, b, filter_size: int):
     """argument checks shared by every entry point; returns (a, b, was_numpy) with NumPy inputs wrapped (not yet uploaded)"""
-    was_numpy = isinstance(a, np.ndarray) and isinstance(b, np.ndarray)
     if isinstance(a, np.ndarray) != isinstance(b, np.ndarray):
         raise ValueError("a and b must both be torch tensors or both be numpy arrays")
-    if was_numpy:
-        a, b = torch.from_numpy(np.ascontiguousarray(a)), torch.from_numpy(np.ascontiguousarray(b))
-    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
-        raise ValueError("a and b must be torch tensors or numpy arrays")
-    if a.dtype != b.dtype:
-        raise ValueError(f"a and b differ in dtype: {a.dtype} and {b.dtype}")
-    if a.dtype not in _DTYPES:
-        raise ValueError(f"images must be uint8 or float32, got {a.dtype}")
-    if a.dim() != 4 or b.dim() != 4:
-        raise ValueError(f"expected [B,H,W,C] batches, got {tuple(a.shape)} and {tuple(b.shape)}")
-    if a.shape != b.shape:
-        raise ValueError(f"a {tuple(a.shape)} and b {tuple(b.shape)} differ in shape")
-    filter_size = int(filter_size)
-    if filter_size < 3 or filter_size > 11 or filter_size % 2 == 0:
-        raise ValueError(f"filter_size must be odd and in 3..11, got {filter_size}")
-    B, H, W, C = a.shape
-    if B < 1 or C < 1 or C > 4:
-        raise ValueError(f"expected at least one image of 1..4 channels, got {tuple(a.shape)}")
-    if H < filter_size or W < filter_size:
-        raise ValueError(f"images of {H} x {W} are smaller than the {filter_size} x {filter_size} window")
-    if not was_numpy and (not a.is_cuda or not b.is_cuda):
-        raise RuntimeError("image_metrics runs on the MI355X: the engine has no CPU execution path")
-    if not was_numpy and a.device != b.device:
-        raise ValueError(f"a and b are on different devices: {a.device} and {b.device}")
+    filter_size = _checked_window(filter_size)
+    (a, was_numpy), (b, _) = (A.host_or_device(t, what, tuple(_DTYPES), min_hw=filter_size) for t, what in ((a, "a"), (b, "b")))
+    if a.dtype != b.dtype or a.shape != b.shape:
+        raise ValueError(f"a and b differ in dtype or shape: {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
     return a, b, was_numpy
 
 
@@ -68,21 +56,14 @@ def image_metric_sums(a, b, max_val: float = 255.0, filter_size: int = 11, filte
     a, b, was_numpy = _as_tensor_pair(a, b, filter_size)
     if not (max_val > 0.0 and filter_sigma > 0.0 and k1 >= 0.0 and k2 >= 0.0):
         raise ValueError("max_val and filter_sigma must be positive, k1 and k2 non-negative")
-    if was_numpy:
-        if not torch.cuda.is_available():
-            raise RuntimeError("image_metrics runs on the MI355X: the engine has no CPU execution path")
-        a, b = a.cuda(), b.cuda()
-    a, b = a.contiguous(), b.contiguous()
+    a, b = (A.to_device(t, was_numpy, None, what, _FEATURE).contiguous() for t, what in ((a, "a"), (b, "b")))
+    if a.device != b.device:
+        raise ValueError(f"a and b are on different devices: {a.device} and {b.device}")
     B, H, W, C = a.shape
-    lib = N.lib()
-    nbytes = lib.bf_image_metrics_scratch_bytes(B, H, W, C, int(filter_size))
-    if nbytes < 0:
-        N.check(int(nbytes), None, "bf_image_metrics_scratch_bytes")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device)
+    scratch, nbytes = N.scratch("bf_image_metrics", a.device, B, H, W, C, int(filter_size))
     out = torch.empty((B, 4), dtype=torch.float64, device=a.device)
-    N.check(lib.bf_image_metrics(N.ptr(a), N.ptr(b), _DTYPES[a.dtype], B, H, W, C, float(max_val), int(filter_size),
-                                 float(filter_sigma), float(k1), float(k2), N.ptr(out), N.ptr(scratch), nbytes, N.stream_ptr(a)),
-            None, "bf_image_metrics")
+    N.call("bf_image_metrics", N.ptr(a), N.ptr(b), _DTYPES[a.dtype], B, H, W, C, float(max_val), int(filter_size),
+           float(filter_sigma), float(k1), float(k2), N.ptr(out), N.ptr(scratch), nbytes, N.stream_ptr(a))
     return out.cpu().numpy() if was_numpy else out
 
 
@@ -133,24 +114,6 @@ def _level_seed(seed: int, level: int, batch: int) -> int:
     return ((int(seed) * 1000003 + level) * 1000003 + batch) & 0x7FFFFFFFFFFFFFFF
 
 
-def _module_device(module):
-    hydra = getattr(module, "model_hydra", None)
-    dev = getattr(hydra, "device", None)
-    if dev is not None and torch.device(dev).type == "cuda":
-        return torch.device(dev)
-    if not torch.cuda.is_available():
-        raise RuntimeError("evaluate runs on the MI355X: the engine has no CPU execution path")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _check_clean_batch(batch) -> torch.Tensor:
-    t = torch.from_numpy(np.ascontiguousarray(batch)) if isinstance(batch, np.ndarray) else batch
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4:
-        raise ValueError(f"clean batches must be uint8 [B,H,W,C] tensors or arrays, got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    return t
-
-
 def _check_noise_std(noise_std) -> List[float]:
     levels = [float(s) for s in noise_std]
     if not levels or any(s < 0.0 for s in levels):
@@ -169,22 +132,16 @@ def evaluate(module, clean_batches: Iterable, noise_std: Sequence[float] = DEFAU
     if not callable(module):
         raise ValueError("module must be callable: uint8 [B,H,W,C] -> uint8 [B,H,W,C]")
     levels = _check_noise_std(noise_std)
-    if int(filter_size) < 3 or int(filter_size) > 11 or int(filter_size) % 2 == 0:
-        raise ValueError(f"filter_size must be odd and in 3..11, got {filter_size}")
-    batches = [_check_clean_batch(b) for b in clean_batches]
-    if not batches:
-        raise ValueError("no clean batches to evaluate on")
-    dev = _module_device(module)
+    _checked_window(filter_size)
+    batches = A.uint8_batches(clean_batches, "clean batches")
+    dev = A.device_of(module, "evaluate")
     batches = [b.to(dev).contiguous() for b in batches]
     report = []
     for li, sigma in enumerate(levels):
         noisy_m, den_m = [], []
         for bi, clean in enumerate(batches):
             noisy = corrupt_u8(clean, sigma, _level_seed(seed, li, bi))
-            denoised = module(noisy)
-            if not isinstance(denoised, torch.Tensor) or denoised.dtype != torch.uint8 or denoised.shape != clean.shape:
-                raise ValueError(f"the module returned {getattr(denoised, 'dtype', type(denoised))} "
-                                 f"{tuple(getattr(denoised, 'shape', ()))} for a uint8 {tuple(clean.shape)} batch")
+            denoised = A.module_result(module(noisy), torch.uint8, clean.shape)
             noisy_m.append(torch.stack(image_metrics(clean, noisy, filter_size=filter_size)))
             den_m.append(torch.stack(image_metrics(clean, denoised, filter_size=filter_size)))
         if hasattr(module, "check_status"):
@@ -218,6 +175,18 @@ def json_safe(value):
     if isinstance(value, float) and not np.isfinite(value):
         return None
     return value
+
+
+def summarise(batches, per_batch_tensors, keys):
+    """the end of every report over batches: (rows, aggregate) from one [len(keys), B] device tensor per batch -- per batch its
+    shape, its number of images and the mean of every key over its images; `aggregate` the same over every image"""
+    with np.errstate(invalid="ignore"):
+        host = [p.cpu().numpy() for p in per_batch_tensors]
+        rows = [{"shape": [int(v) for v in b.shape], "images": int(h.shape[1]), **{k: float(h[i].mean()) for i, k in enumerate(keys)}}
+                for b, h in zip(batches, host)]
+        every = np.concatenate(host, axis=1)
+        aggregate = {"images": int(every.shape[1]), **{k: float(every[i].mean()) for i, k in enumerate(keys)}}
+    return rows, aggregate
 
 
 # ---- validation inside train_loop ---------------------------------------------------------------
@@ -258,37 +227,46 @@ def load_evaluation_batches(inputs: Sequence[str], no_images: int, input_shape: 
     return [np.clip(np.round(np.stack(images)), 0, 255).astype(np.uint8)]
 
 
-class Evaluator:
-    """`evaluate` on a fixed set of images with a fixed seed, so that successive records are comparable.  It runs the current
-    weights through the inference path (DenoiserModule re-packs after an optimizer step) and touches nothing a training step
-    reads: no BatchNorm statistics, no optimizer slot, no random stream of the dataset."""
+class PeriodicValidator:
+    """A report on a fixed set of images with a fixed seed, so that successive records are comparable, called by `train_loop`
+    between optimizer steps.  It runs the current weights through the inference path (DenoiserModule re-packs after an optimizer
+    step) and touches nothing a training step reads: no BatchNorm statistics, no optimizer slot, no random stream of the dataset.
+    A subclass names its file, its batches (what, min_hw, the message for none) and has `run(step, epoch)`."""
+    FILE, BATCHES = None, None
 
-    def __init__(self, model, config: EvaluationConfig, batches: Iterable, model_dir: Optional[str] = None, seed: int = 0):
-        from .module_denoiser import DenoiserModule
+    def __init__(self, model, config, batches: Iterable, model_dir: Optional[str] = None, seed: int = 0):
         self.config, self.seed = config, int(seed)
         self.module = DenoiserModule(model)
-        self.batches = [_check_clean_batch(b) for b in batches]
-        if not self.batches:
-            raise ValueError("train.evaluation needs images: name `inputs` directories or pass evaluation_batches")
+        self.batches = A.uint8_batches(batches, *self.BATCHES)
         if getattr(model, "device", None) is not None and torch.device(model.device).type == "cuda":
             self.batches = [b.to(model.device) for b in self.batches]          # loaded once, kept on the device as uint8
-        self.path = None if model_dir is None else os.path.join(model_dir, "evaluation.jsonl")
+        self.path = None if model_dir is None else os.path.join(model_dir, self.FILE)
         self.history: List[Dict] = []
 
     def due(self, step: int) -> bool:
         return self.config.every > 0 and step > 0 and step % self.config.every == 0
 
-    def run(self, step: int, epoch: int) -> Dict:
-        record = {"step": int(step), "epoch": int(epoch), "levels": evaluate(self.module, self.batches, self.config.noise_std, self.seed)}
+    def _keep(self, record: Dict) -> Dict:
+        """appends the record to the history and, as one line of strict JSON, to the file"""
         self.history.append(record)
-        for r in record["levels"]:
-            logger.info(f"evaluation step {step} sigma {r['noise_std']:g}: psnr {r['psnr_noisy']:.3f} -> {r['psnr_denoised']:.3f}, "
-                        f"ssim {r['ssim_noisy']:.5f} -> {r['ssim_denoised']:.5f}, mae {r['mae_noisy']:.3f} -> {r['mae_denoised']:.3f}")
         if self.path is not None:
             os.makedirs(os.path.dirname(self.path), exist_ok=True)
             with open(self.path, "a") as f:
                 f.write(json.dumps(json_safe(record), allow_nan=False) + "\n")
         return record
+
+
+class Evaluator(PeriodicValidator):
+    """`evaluate` as a PeriodicValidator: what a run that has clean images validates with."""
+    FILE = "evaluation.jsonl"
+    BATCHES = ("clean batches", 1, "train.evaluation needs images: name `inputs` directories or pass evaluation_batches")
+
+    def run(self, step: int, epoch: int) -> Dict:
+        record = {"step": int(step), "epoch": int(epoch), "levels": evaluate(self.module, self.batches, self.config.noise_std, self.seed)}
+        for r in record["levels"]:
+            logger.info(f"evaluation step {step} sigma {r['noise_std']:g}: psnr {r['psnr_noisy']:.3f} -> {r['psnr_denoised']:.3f}, "
+                        f"ssim {r['ssim_noisy']:.5f} -> {r['ssim_denoised']:.5f}, mae {r['mae_noisy']:.3f} -> {r['mae_denoised']:.3f}")
+        return self._keep(record)
 
 
 def build_evaluator(train_config: Dict, model, model_dir: Optional[str] = None, dataset_config: Optional[Dict] = None,

@@ -1,7 +1,7 @@
 """DenoiserModule: the inference drop-in boundary (bfcnn/module_denoiser.py:15-75)."""
-import numpy as np
 import torch
 
+from . import _args as A
 from .constants import DENOISER_STR
 
 
@@ -98,18 +98,15 @@ class DenoiserModule:
 
     def _checked_input(self, image):
         """the argument checks of a call: (image as a uint8 [B,H,W,C] torch tensor, whether a numpy array was given)"""
-        was_numpy = isinstance(image, np.ndarray)
-        if was_numpy:
-            image = torch.from_numpy(np.ascontiguousarray(image))
-        if not isinstance(image, torch.Tensor):
-            raise ValueError("image must be a torch.Tensor or numpy array")
-        if image.dtype != torch.uint8 or image.dim() != 4:
-            raise ValueError(f"input must be a uint8 tensor of shape [B,H,W,C], "
-                             f"got {image.dtype} {tuple(image.shape)}")
-        hydra = self._model_hydra
-        if image.shape[-1] != hydra.desc.in_channels:
-            raise ValueError(f"expected {hydra.desc.in_channels} channels, got {image.shape[-1]}")
-        return image, was_numpy
+        channels = self._model_hydra.desc.in_channels
+        return A.host_or_device(image, "image", (torch.uint8,), min_hw=0, allow_empty=True, channels=(channels, channels))
+
+    def float_form(self) -> "DenoiserModule":
+        """this module without the rounding: uint8 -> float32.  It shares the record of pending status words, so that
+        check_status() of either sees the calls of both"""
+        inner = DenoiserModule(self._model_hydra, cast_to_uint8=False)
+        inner._deferred = self._deferred
+        return inner
 
     def _empty_output(self, image: torch.Tensor, was_numpy: bool):
         """what a call returns for a batch of no images"""
@@ -205,18 +202,13 @@ class GraphedDenoiserModule:
             static_out = self._module(static_in)
         return graph, static_in, static_out, self._stamp()
 
+    def float_form(self) -> DenoiserModule:
+        """the float form of the wrapped module, called directly (a rounded graph output cannot be un-rounded)"""
+        return self._module.float_form()
+
     def __call__(self, image):
-        was_numpy = isinstance(image, np.ndarray)
-        if was_numpy:
-            image = torch.from_numpy(np.ascontiguousarray(image))
-        if not isinstance(image, torch.Tensor):
-            raise ValueError("image must be a torch.Tensor or numpy array")
-        if image.dtype != torch.uint8 or image.dim() != 4:
-            raise ValueError(f"input must be a uint8 tensor of shape [B,H,W,C], "
-                             f"got {image.dtype} {tuple(image.shape)}")
+        image, was_numpy = self._module._checked_input(image)
         hydra = self._module.model_hydra
-        if image.shape[-1] != hydra.desc.in_channels:
-            raise ValueError(f"expected {hydra.desc.in_channels} channels, got {image.shape[-1]}")
         if image.shape[0] == 0:
             return self._module(image.numpy() if was_numpy else image)
         hydra._require_gpu()
@@ -245,3 +237,15 @@ class GraphedDenoiserModule:
         if st is not None:
             self._module._deferred.post(st)
         return static_out.clone() if self._copy else static_out
+
+
+def float_form(module, what: str = "module"):
+    """The float form of `module`: uint8 [B,H,W,C] device tensor -> float32 of the same shape, not rounded.  A wrapper class
+    answers for itself (its `float_form()`); any other callable is taken to be that function already."""
+    method = getattr(module, "float_form", None)
+    if callable(method):
+        return method()
+    if not callable(module):
+        raise ValueError(f"{what} must be a DenoiserModule, one of its wrappers (graphed, self-ensemble, stabilised) or a "
+                         f"callable uint8 [B,H,W,C] -> float32 [B,H,W,C]")
+    return module

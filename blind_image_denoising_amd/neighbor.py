@@ -20,36 +20,23 @@ One kernel (`bf_op_neighbor_pairs`, csrc/neighbor.hip) builds both tensors from 
 front of `train_loop` (`train.self_supervised`), and `RiskValidator` validates such a run by SURE (risk.py), since nobody has clean
 images to validate on.  DESIGN.md 7.9 has the contract and the measurements.
 """
-import json
 import math
-import os
 from collections import namedtuple
-from typing import Dict, Iterable, List, Optional, Tuple
+from typing import Dict, Iterable, Optional, Tuple
 
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _native as N
 from .custom_logger import logger
+from .metrics import PeriodicValidator, load_evaluation_batches
+from .module_denoiser import DenoiserModule, float_form
+from .noise_estimate import METHODS
+from .risk import MAX_PROBES, evaluate_blind_risk
 
 _DTYPES = (torch.uint8, torch.float32)
-
-
-def _checked_seed(seed) -> int:
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed must be an int in 0..2^64-1, got {seed!r}")
-    return int(seed)
-
-
-def _checked_batch(t, what: str):
-    if not isinstance(t, torch.Tensor) or t.dtype not in _DTYPES or t.dim() != 4:
-        raise ValueError(f"{what} must be a uint8 or float32 tensor of shape [B,H,W,C], got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    B, H, W, C = t.shape
-    if B < 1 or H < 2 or W < 2 or H % 2 or W % 2:
-        raise ValueError(f"{what} must hold at least one image of even height and width (2x2 cells), got {tuple(t.shape)}")
-    if not 1 <= C <= 4:
-        raise ValueError(f"{what} must have 1..4 channels, got {tuple(t.shape)}")
+_FEATURE = "the pair kernel"
 
 
 def neighbor_pairs(noisy: torch.Tensor, seed: int = 0, denoised: Optional[torch.Tensor] = None,
@@ -58,8 +45,8 @@ def neighbor_pairs(noisy: torch.Tensor, seed: int = 0, denoised: Optional[torch.
     float32 [B,H/2,W/2,C].  In every 2x2 cell an ordered pair (p1, p2) of adjacent pixels is drawn from Philox (seed, image, cell):
     input = y[p1]; target = y[p2], or with `denoised` = f(y) (float32, the shape of y) fmaf(weight, f[p1] - f[p2], y[p2]), `weight` =
     lambda in [0, 1).  The same seed draws the same pairs for every tensor of the shape: neighbor_pairs(f, seed) is (g1(f), g2(f))."""
-    seed = _checked_seed(seed)
-    _checked_batch(noisy, "noisy")
+    seed = A.seed64(seed)
+    A.image_batch(noisy, "noisy", _DTYPES, min_hw=2, even=True)
     if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)) or not math.isfinite(weight) \
             or not 0.0 <= float(np.float32(weight)) < 1.0:
         raise ValueError(f"weight must be a float in [0, 1), got {weight!r}")
@@ -69,9 +56,7 @@ def neighbor_pairs(noisy: torch.Tensor, seed: int = 0, denoised: Optional[torch.
                              f"{getattr(denoised, 'dtype', type(denoised))} {tuple(getattr(denoised, 'shape', ()))}")
         if denoised.device != noisy.device:
             raise ValueError(f"denoised lives on {denoised.device}, noisy on {noisy.device}")
-    if not noisy.is_cuda:
-        raise RuntimeError("noisy must live on the GPU: the pair kernel has no CPU execution path")
-    noisy = noisy.contiguous()
+    noisy = A.to_device(noisy, False, None, "noisy", _FEATURE).contiguous()
     denoised = None if denoised is None else denoised.contiguous()
     B, H, W, C = noisy.shape
     inp = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=noisy.device)
@@ -79,17 +64,6 @@ def neighbor_pairs(noisy: torch.Tensor, seed: int = 0, denoised: Optional[torch.
     N.call("bf_op_neighbor_pairs", N.ptr(noisy), int(noisy.dtype == torch.uint8), N.ptr(denoised), float(weight), N.ptr(inp),
            N.ptr(tgt), B, H, W, C, seed, N.stream_ptr(noisy))
     return inp, tgt
-
-
-def _float_forward(model):
-    """uint8 [B,H,W,C] -> float32 of the same shape for `model`: DenoiserModule(model, cast_to_uint8=False) for a hydra; any other
-    callable is taken as that function itself (tests put a counting stub here)"""
-    if hasattr(model, "infer_u8"):
-        from .module_denoiser import DenoiserModule
-        return DenoiserModule(model, cast_to_uint8=False)
-    if not callable(model):
-        raise ValueError("model must be a hydra or a callable uint8 [B,H,W,C] -> float32 [B,H,W,C]")
-    return model
 
 
 class NeighborPairs:
@@ -106,14 +80,17 @@ class NeighborPairs:
     under no-grad); its f16-range status is the module's own (`check_status`).  With lambda = 0 no forward is run at all."""
 
     def __init__(self, batches: Iterable, model=None, gamma: float = 0.0, ramp: bool = True, seed: Optional[int] = None):
-        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) or not math.isfinite(gamma) or gamma < 0:
-            raise ValueError(f"gamma must be a finite float >= 0, got {gamma!r}")
+        gamma = A.non_negative_float(gamma, "gamma")
         if batches is None or not hasattr(batches, "__iter__"):
             raise ValueError("batches must be an iterable of noisy batches or of (anything, noisy) pairs")
-        if float(gamma) > 0.0 and model is None:
+        if gamma > 0.0 and model is None:
             raise ValueError("gamma > 0 needs the model whose output the regulariser compares")
-        self.batches, self.gamma, self.ramp = batches, float(gamma), bool(ramp)
-        self.forward = _float_forward(model) if float(gamma) > 0.0 else None
+        self.batches, self.gamma, self.ramp = batches, gamma, bool(ramp)
+        # a hydra runs as DenoiserModule(model, cast_to_uint8=False); any other callable is that function itself (tests put a
+        # counting stub here)
+        self.forward = None
+        if gamma > 0.0:
+            self.forward = DenoiserModule(model, cast_to_uint8=False) if hasattr(model, "infer_u8") else float_form(model, "model")
         self.device = getattr(model, "device", None)
         self.rng = np.random.default_rng(seed)
         self.percentage_done = 0.0
@@ -131,8 +108,7 @@ class NeighborPairs:
             if len(item) != 2:
                 raise ValueError(f"a batch must be a noisy tensor or an (anything, noisy) pair, got a sequence of {len(item)}")
             item = item[1]
-        t = torch.from_numpy(np.ascontiguousarray(item)) if isinstance(item, np.ndarray) else item
-        _checked_batch(t, "a noisy batch")
+        t, _ = A.host_or_device(item, "a noisy batch", _DTYPES, min_hw=2, even=True)
         if not t.is_cuda:
             t = t.to(self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device()))
         return t
@@ -143,10 +119,7 @@ class NeighborPairs:
             seed, lam, f = int(self.rng.integers(0, 2 ** 63 - 1)), self.weight(), None
             if lam > 0.0:
                 y_u8 = y if y.dtype == torch.uint8 else y.round().clamp_(0.0, 255.0).to(torch.uint8)
-                f = self.forward(y_u8)
-                if not isinstance(f, torch.Tensor) or f.dtype != torch.float32 or f.shape != y.shape:
-                    raise ValueError(f"the model returned {getattr(f, 'dtype', type(f))} {tuple(getattr(f, 'shape', ()))} for a uint8 "
-                                     f"{tuple(y.shape)} batch; float32 of the same shape is needed")
+                f = A.module_result(self.forward(y_u8), torch.float32, y.shape)
             inp, tgt = neighbor_pairs(y, seed, f, lam)
             yield tgt, inp
         self.check_status(wait=True)
@@ -168,17 +141,14 @@ def _parse_validation(section) -> Optional[RiskValidationConfig]:
     unknown = set(section) - set(RiskValidationConfig._fields)
     if unknown:
         raise ValueError(f"unknown keys in train.self_supervised.validation: {sorted(unknown)}")
-    from .risk import _checked_probe
-    from .noise_estimate import _checked_method
     inputs = section.get("inputs", [])
     inputs = [inputs] if isinstance(inputs, str) else list(inputs)
     sigma = section.get("sigma")
-    if sigma is not None and (isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not math.isfinite(sigma) or sigma < 0):
-        raise ValueError(f"train.self_supervised.validation.sigma must be null or a non-negative float, got {sigma!r}")
-    probes, _, _ = _checked_probe(section.get("probes", 1), 1, 0)
-    return RiskValidationConfig(every=max(0, int(section.get("every", 0))), inputs=[str(i) for i in inputs],
-                                sigma=None if sigma is None else float(sigma), method=_checked_method(section.get("method", "mad")),
-                                probes=probes)
+    if sigma is not None:
+        sigma = A.non_negative_float(sigma, "train.self_supervised.validation.sigma")
+    return RiskValidationConfig(every=max(0, int(section.get("every", 0))), inputs=[str(i) for i in inputs], sigma=sigma,
+                                method=A.one_of(section.get("method", "mad"), "train.self_supervised.validation.method", METHODS),
+                                probes=A.int_in(section.get("probes", 1), "train.self_supervised.validation.probes", 1, MAX_PROBES))
 
 
 def parse_self_supervised_config(train_config: Dict) -> Optional[SelfSupervisedConfig]:
@@ -197,50 +167,25 @@ def parse_self_supervised_config(train_config: Dict) -> Optional[SelfSupervisedC
     unknown = set(section) - set(SelfSupervisedConfig._fields)
     if unknown:
         raise ValueError(f"unknown keys in train.self_supervised: {sorted(unknown)}")
-    gamma = section.get("gamma", 0.0)
-    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma) or gamma < 0:
-        raise ValueError(f"train.self_supervised.gamma must be a finite float >= 0, got {gamma!r}")
+    gamma = A.non_negative_float(section.get("gamma", 0.0), "train.self_supervised.gamma")
     ramp = section.get("ramp", True)
     if not isinstance(ramp, bool):
         raise ValueError(f"train.self_supervised.ramp must be true or false, got {ramp!r}")
-    return SelfSupervisedConfig(kind, float(gamma), ramp, _parse_validation(section.get("validation")))
+    return SelfSupervisedConfig(kind, gamma, ramp, _parse_validation(section.get("validation")))
 
 
-class RiskValidator:
-    """`evaluate_blind_risk` on a fixed set of noisy images with a fixed seed, so that successive records are comparable: what
-    metrics.Evaluator is to a run that has clean images.  It runs the current weights through the inference path and touches
-    nothing a training step reads."""
-
-    def __init__(self, model, config: RiskValidationConfig, batches: Iterable, model_dir: Optional[str] = None, seed: int = 0):
-        from .module_denoiser import DenoiserModule
-        from .noise_estimate import _check_noisy_batch
-        self.config, self.seed = config, int(seed)
-        self.module = DenoiserModule(model)
-        self.batches = [_check_noisy_batch(b) for b in batches]
-        if not self.batches:
-            raise ValueError("train.self_supervised.validation needs images: name `inputs` directories or pass validation_noisy_batches")
-        if getattr(model, "device", None) is not None and torch.device(model.device).type == "cuda":
-            self.batches = [b.to(model.device) for b in self.batches]
-        self.path = None if model_dir is None else os.path.join(model_dir, "risk.jsonl")
-        self.history: List[Dict] = []
-
-    def due(self, step: int) -> bool:
-        return self.config.every > 0 and step > 0 and step % self.config.every == 0
+class RiskValidator(PeriodicValidator):
+    """`evaluate_blind_risk` as a PeriodicValidator: what metrics.Evaluator is to a run that has clean images."""
+    FILE = "risk.jsonl"
+    BATCHES = ("noisy batches", 3,
+               "train.self_supervised.validation needs images: name `inputs` directories or pass validation_noisy_batches")
 
     def run(self, step: int, epoch: int) -> Dict:
-        from .metrics import json_safe
-        from .risk import evaluate_blind_risk
         c = self.config
         report = evaluate_blind_risk(self.module, self.batches, sigma=c.sigma, method=c.method, probes=c.probes, seed=self.seed)
-        record = {"step": int(step), "epoch": int(epoch), "risk": report}
-        self.history.append(record)
         a = report["aggregate"]
         logger.info(f"risk step {step}: sigma in {a['sigma_in']:.3f}, estimated mse {a['mse']:.3f}, estimated psnr {a['psnr']:.3f}")
-        if self.path is not None:
-            os.makedirs(os.path.dirname(self.path), exist_ok=True)
-            with open(self.path, "a") as f:
-                f.write(json.dumps(json_safe(record), allow_nan=False) + "\n")
-        return record
+        return self._keep({"step": int(step), "epoch": int(epoch), "risk": report})
 
 
 def build_risk_validator(config: Optional[SelfSupervisedConfig], model, model_dir: Optional[str] = None,
@@ -257,6 +202,5 @@ def build_risk_validator(config: Optional[SelfSupervisedConfig], model, model_di
         shape = (dataset_config or {}).get("input_shape")
         if shape is None:
             raise ValueError("train.self_supervised.validation.inputs needs dataset.input_shape for the size the images are loaded at")
-        from .metrics import load_evaluation_batches
         validation_noisy_batches = load_evaluation_batches(v.inputs, VALIDATION_IMAGES, shape, int(model.desc.in_channels))
     return RiskValidator(model, v, validation_noisy_batches, model_dir)

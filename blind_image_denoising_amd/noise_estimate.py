@@ -15,65 +15,33 @@ the size of the noise that was there (ratio = removed_rms / sigma_in, near 1 whe
 from collections import namedtuple
 from typing import Dict, Iterable
 
-import numpy as np
 import torch
 
+from . import _args as A
 from . import _native as N
-from .metrics import _module_device, image_metric_sums
+from .metrics import image_metric_sums, summarise
 
 NoiseEstimate = namedtuple("NoiseEstimate", ["sigma_fast", "sigma_mad", "clipped_fraction"])
 
 METHODS = ("mad", "immerkaer")
 _DTYPES = {torch.uint8: N.BF_DTYPE_U8, torch.float32: N.BF_DTYPE_F32}
-_NO_GPU = "noise_statistics runs on the MI355X: the engine has no CPU execution path"
+_FEATURE = "noise_statistics"
 
 
 def _checked_images(images):
     """the argument checks of every entry point, before the GPU is touched: (images as a torch tensor, whether NumPy was given)"""
-    was_numpy = isinstance(images, np.ndarray)
-    if was_numpy:
-        if images.dtype not in (np.uint8, np.float32):
-            raise ValueError(f"images must be uint8 or float32, got {images.dtype}")
-        images = torch.from_numpy(np.ascontiguousarray(images))
-    if not isinstance(images, torch.Tensor):
-        raise ValueError("images must be a torch tensor or a numpy array")
-    if images.dtype not in _DTYPES:
-        raise ValueError(f"images must be uint8 or float32, got {images.dtype}")
-    if images.dim() != 4:
-        raise ValueError(f"expected a [B,H,W,C] batch, got {tuple(images.shape)}")
-    _, H, W, C = images.shape
-    if C < 1 or C > 4:
-        raise ValueError(f"expected 1..4 channels, got {tuple(images.shape)}")
-    if H < 3 or W < 3:
-        raise ValueError(f"images of {H} x {W} are smaller than the 3 x 3 mask of the estimator")
-    return images, was_numpy
-
-
-def _checked_method(method: str) -> str:
-    if method not in METHODS:
-        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
-    return method
+    return A.host_or_device(images, "images", tuple(_DTYPES), min_hw=3, allow_empty=True)
 
 
 def _statistics(images: torch.Tensor, was_numpy: bool) -> torch.Tensor:
     B, H, W, C = images.shape
     if B == 0:                                                   # nothing to launch
         return torch.empty((0, C, 4), dtype=torch.float64, device=images.device)
-    if was_numpy:
-        if not torch.cuda.is_available():
-            raise RuntimeError(_NO_GPU)
-        images = images.cuda()
-    elif not images.is_cuda:
-        raise RuntimeError(_NO_GPU)
-    images = images.contiguous()
-    lib = N.lib()
-    nbytes = lib.bf_noise_estimate_scratch_bytes(B, H, W, C)
-    if nbytes < 0:
-        N.check(int(nbytes), None, "bf_noise_estimate_scratch_bytes")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=images.device)
+    images = A.to_device(images, was_numpy, None, "images", _FEATURE).contiguous()
+    scratch, nbytes = N.scratch("bf_noise_estimate", images.device, B, H, W, C)
     out = torch.empty((B, C, 4), dtype=torch.float64, device=images.device)
-    N.check(lib.bf_noise_estimate(N.ptr(images), _DTYPES[images.dtype], B, H, W, C, N.ptr(scratch), nbytes, N.ptr(out),
-                                  N.stream_ptr(images)), None, "bf_noise_estimate")
+    N.call("bf_noise_estimate", N.ptr(images), _DTYPES[images.dtype], B, H, W, C, N.ptr(scratch), nbytes, N.ptr(out),
+           N.stream_ptr(images))
     return out
 
 
@@ -98,7 +66,7 @@ def estimate_noise(images, method: str = "mad", per_channel: bool = False):
     `per_channel`.  method "mad": the median of the finest diagonal Haar band / 0.6745 (uint8 images only: it needs the exact
     histogram); "immerkaer": the mean absolute response of the Laplacian-difference mask.  The channels are combined as the root
     mean square of their sigmas.  float64 tensors on the images' device, NumPy arrays for NumPy images."""
-    method = _checked_method(method)
+    method = A.one_of(method, "method", METHODS)
     images, was_numpy = _checked_images(images)
     if method == "mad" and images.dtype != torch.uint8:
         raise ValueError('method "mad" needs uint8 images (the exact histogram of the Haar band); use method="immerkaer" for float32')
@@ -113,17 +81,6 @@ def estimate_noise(images, method: str = "mad", per_channel: bool = False):
 _KEYS = ("sigma_in", "sigma_out", "removed_rms", "ratio", "clipped_fraction")
 
 
-def _check_noisy_batch(batch) -> torch.Tensor:
-    t = torch.from_numpy(np.ascontiguousarray(batch)) if isinstance(batch, np.ndarray) else batch
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4:
-        raise ValueError(f"noisy batches must be uint8 [B,H,W,C] tensors or arrays, got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    t, _ = _checked_images(t)
-    if t.shape[0] < 1:
-        raise ValueError("a noisy batch holds no image")
-    return t
-
-
 def evaluate_blind(module, noisy_batches: Iterable, method: str = "mad") -> Dict:
     """A blind denoiser on images that are already noisy.  `module`: callable uint8 [B,H,W,C] -> uint8 of the same shape
     (DenoiserModule, GraphedDenoiserModule, SelfEnsembleDenoiserModule); `noisy_batches`: an iterable of uint8 batches, host or
@@ -133,18 +90,13 @@ def evaluate_blind(module, noisy_batches: Iterable, method: str = "mad") -> Dict
     samples.  Nothing is asserted; the module's deferred f16-range status is checked once at the end."""
     if not callable(module):
         raise ValueError("module must be callable: uint8 [B,H,W,C] -> uint8 [B,H,W,C]")
-    method = _checked_method(method)
-    batches = [_check_noisy_batch(b) for b in noisy_batches]
-    if not batches:
-        raise ValueError("no noisy batches to evaluate on")
-    dev = _module_device(module)
+    method = A.one_of(method, "method", METHODS)
+    batches = A.uint8_batches(noisy_batches, "noisy batches", min_hw=3)
+    dev = A.device_of(module, "evaluate_blind")
     per_image = []                                               # one [5, B] device tensor per batch, rows as _KEYS
     for noisy in batches:
         noisy = noisy.to(dev).contiguous()
-        denoised = module(noisy)
-        if not isinstance(denoised, torch.Tensor) or denoised.dtype != torch.uint8 or denoised.shape != noisy.shape:
-            raise ValueError(f"the module returned {getattr(denoised, 'dtype', type(denoised))} "
-                             f"{tuple(getattr(denoised, 'shape', ()))} for a uint8 {tuple(noisy.shape)} batch")
+        denoised = A.module_result(module(noisy), torch.uint8, noisy.shape)
         stats_in = noise_statistics(noisy)
         column = 2 if method == "mad" else 1
         sigma_in = torch.sqrt((stats_in[:, :, column] ** 2).mean(dim=1))
@@ -155,13 +107,7 @@ def evaluate_blind(module, noisy_batches: Iterable, method: str = "mad") -> Dict
         per_image.append(torch.stack([sigma_in, sigma_out, removed, removed / sigma_in, clipped]))
     if hasattr(module, "check_status"):
         module.check_status()                                    # an overflow of the split-f16 kernels is not averaged into a number
-    rows = []
-    with np.errstate(invalid="ignore"):
-        host = [p.cpu().numpy() for p in per_image]
-        for noisy, h in zip(batches, host):
-            rows.append({"shape": [int(v) for v in noisy.shape], "images": int(h.shape[1]), **{k: float(h[i].mean()) for i, k in enumerate(_KEYS)}})
-        every = np.concatenate(host, axis=1)
-        aggregate = {"images": int(every.shape[1]), **{k: float(every[i].mean()) for i, k in enumerate(_KEYS)}}
+    rows, aggregate = summarise(batches, per_image, _KEYS)
     return {"method": method, "images": aggregate["images"], "batches": rows, "aggregate": aggregate}
 
 

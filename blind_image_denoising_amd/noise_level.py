@@ -19,11 +19,12 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _native as N
-from .noise_estimate import _checked_images, noise_statistics
+from .noise_estimate import noise_statistics
 
 LEVELS = 16
-_NO_GPU = "the noise level kernels run on the MI355X: the engine has no CPU execution path"
+_FEATURE = "the noise level code for the MI355X"
 
 _Fields = namedtuple("NoiseLevelFunction", ["gain", "offset", "level_mean", "level_sigma", "level_count", "excluded_fraction"])
 
@@ -43,9 +44,8 @@ class NoiseLevelFunction(_Fields):
 
 
 def _checked_u8(images):
-    if isinstance(images, (np.ndarray, torch.Tensor)) and images.dtype not in (np.uint8, torch.uint8):
-        raise ValueError(f"images must be uint8 (the levels are exact histograms of integers), got {images.dtype}")
-    return _checked_images(images)
+    """uint8 only: the levels are exact histograms of integers"""
+    return A.host_or_device(images, "images", (torch.uint8,), min_hw=3, allow_empty=True)
 
 
 def _statistics(images: torch.Tensor, was_numpy: bool):
@@ -53,22 +53,11 @@ def _statistics(images: torch.Tensor, was_numpy: bool):
     if B == 0:                                                   # nothing to launch
         return (torch.empty((0, C, LEVELS, 3), dtype=torch.float64, device=images.device),
                 torch.empty((0, C), dtype=torch.float64, device=images.device))
-    if was_numpy:
-        if not torch.cuda.is_available():
-            raise RuntimeError(_NO_GPU)
-        images = images.cuda()
-    elif not images.is_cuda:
-        raise RuntimeError(_NO_GPU)
-    images = images.contiguous()
-    lib = N.lib()
-    nbytes = lib.bf_noise_level_scratch_bytes(B, H, W, C)
-    if nbytes < 0:
-        N.check(int(nbytes), None, "bf_noise_level_scratch_bytes")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=images.device)
+    images = A.to_device(images, was_numpy, None, "images", _FEATURE).contiguous()
+    scratch, nbytes = N.scratch("bf_noise_level", images.device, B, H, W, C)
     levels = torch.empty((B, C, LEVELS, 3), dtype=torch.float64, device=images.device)
     excluded = torch.empty((B, C), dtype=torch.float64, device=images.device)
-    N.check(lib.bf_noise_level(N.ptr(images), B, H, W, C, N.ptr(scratch), nbytes, N.ptr(levels), N.ptr(excluded),
-                               N.stream_ptr(images)), None, "bf_noise_level")
+    N.call("bf_noise_level", N.ptr(images), B, H, W, C, N.ptr(scratch), nbytes, N.ptr(levels), N.ptr(excluded), N.stream_ptr(images))
     return levels, excluded
 
 
@@ -117,8 +106,7 @@ def noise_level_function(images, min_cells: int = 64) -> NoiseLevelFunction:
     NumPy): the fit of fit_noise_levels on noise_level_statistics(images); with no usable level at all the offset is
     noise_statistics' sigma_mad^2.  Clipping at 0 and 255 is not modelled: cells that touch either end are excluded, and levels
     next to the ends still see a one-sided tail."""
-    if isinstance(min_cells, bool) or not isinstance(min_cells, (int, np.integer)) or min_cells < 1:
-        raise ValueError(f"min_cells must be a positive int, got {min_cells!r}")
+    min_cells = A.int_in(min_cells, "min_cells", 1)
     images, was_numpy = _checked_u8(images)
     levels, excluded = _statistics(images, was_numpy)
     B, H, W, C = images.shape
@@ -126,7 +114,7 @@ def noise_level_function(images, min_cells: int = 64) -> NoiseLevelFunction:
         fallback = torch.empty((0, C), dtype=torch.float64, device=levels.device)
     else:
         fallback = noise_statistics(images.to(levels.device))[:, :, 2] ** 2
-    gain, offset, _ = fit_noise_levels(levels, fallback, int(min_cells))
+    gain, offset, _ = fit_noise_levels(levels, fallback, min_cells)
     n, sum_s, sigma = levels[..., 0], levels[..., 1], levels[..., 2]
     used = n > 0
     nan = torch.full_like(n, float("nan"))
@@ -157,20 +145,12 @@ def camera_noise(clean_u8: torch.Tensor, gain, read_sigma, seed: int = 0) -> tor
     z from Box-Muller on Philox (seed, the sample's index inside its image): an image gets the same noise alone or inside a
     batch.  `gain` and `read_sigma`: a float or [C] each, in grey levels (as float32 in the kernel).  Negative or non-finite
     parameters and non-uint8 input raise ValueError before the GPU is touched."""
-    if not isinstance(clean_u8, torch.Tensor) or clean_u8.dtype != torch.uint8 or clean_u8.dim() != 4:
-        raise ValueError(f"clean_u8 must be a uint8 tensor of shape [B,H,W,C], got "
-                         f"{getattr(clean_u8, 'dtype', type(clean_u8))} {tuple(getattr(clean_u8, 'shape', ()))}")
-    B, H, W, C = clean_u8.shape
-    if not 1 <= C <= 4 or B < 1 or H < 1 or W < 1:
-        raise ValueError(f"clean_u8 must be a non-empty [B,H,W,C] batch with 1..4 channels, got {tuple(clean_u8.shape)}")
+    B, H, W, C = A.image_batch(clean_u8, "clean_u8", (torch.uint8,)).shape
     g = _checked_channel_parameter(gain, C, "gain")
     r = _checked_channel_parameter(read_sigma, C, "read_sigma")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed must be an int in 0..2^64-1, got {seed!r}")
-    if not clean_u8.is_cuda:
-        raise RuntimeError(_NO_GPU)
-    clean_u8 = clean_u8.contiguous()
+    seed = A.seed64(seed)
+    clean_u8 = A.to_device(clean_u8, False, None, "clean_u8", _FEATURE).contiguous()
     out = torch.empty_like(clean_u8)
-    N.call("bf_op_camera_noise_u8", N.ptr(clean_u8), N.ptr(out), B, H, W, C, g.ctypes.data, r.ctypes.data, int(seed),
+    N.call("bf_op_camera_noise_u8", N.ptr(clean_u8), N.ptr(out), B, H, W, C, g.ctypes.data, r.ctypes.data, seed,
            N.stream_ptr(clean_u8))
     return out

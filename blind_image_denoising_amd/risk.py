@@ -26,42 +26,21 @@ from typing import Dict, Iterable
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _native as N
-from .metrics import _module_device
-from .module_denoiser import DenoiserModule, GraphedDenoiserModule
-from .noise_estimate import METHODS, _check_noisy_batch, _checked_method, noise_statistics
+from .metrics import summarise
+from .module_denoiser import float_form
+from .noise_estimate import METHODS, noise_statistics
 from .noise_level import NoiseLevelFunction, noise_level_function
-from .self_ensemble import SelfEnsembleDenoiserModule
-from .vst import StabilisedDenoiserModule
 
 RiskEstimate = namedtuple("RiskEstimate", ["mse", "psnr", "sigma", "residual_rms", "divergence", "probe_spread", "sums"])
 
 MAX_PROBES, MAX_AMPLITUDE = 8, 16
+_FEATURE = "the risk estimate"
 
 
 def _checked_probe(probes, amplitude, seed):
-    for value, what, top in ((probes, "probes", MAX_PROBES), (amplitude, "amplitude", MAX_AMPLITUDE)):
-        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= top:
-            raise ValueError(f"{what} must be an int in 1..{top}, got {value!r}")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError(f"seed must be an int in 0..2^64-1, got {seed!r}")
-    return int(probes), int(amplitude), int(seed)
-
-
-def _require_tensor(t, dtype, what: str):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 4:
-        raise ValueError(f"{what} must be a {dtype} tensor of shape [B,H,W,C], got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    if not 1 <= t.shape[3] <= 4:
-        raise ValueError(f"{what} must have 1..4 channels, got {tuple(t.shape)}")
-    if t.shape[0] < 1 or t.shape[1] < 1 or t.shape[2] < 1:
-        raise ValueError(f"{what} must not be empty, got {tuple(t.shape)}")
-
-
-def _require_device(t, dtype, what: str):
-    _require_tensor(t, dtype, what)
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} must live on the GPU: the risk kernels have no CPU execution path")
+    return A.int_in(probes, "probes", 1, MAX_PROBES), A.int_in(amplitude, "amplitude", 1, MAX_AMPLITUDE), A.seed64(seed)
 
 
 def risk_probe_stack_u8(image_u8: torch.Tensor, probes: int = 1, amplitude: int = 1, seed: int = 0) -> torch.Tensor:
@@ -69,8 +48,7 @@ def risk_probe_stack_u8(image_u8: torch.Tensor, probes: int = 1, amplitude: int 
     is the image, member p = 1..probes the image + amplitude * s_p, s_p = +-1 per sample from Philox (seed, p, sample index),
     reflected where it would leave 0..255.  The signs of an image do not depend on its place in the batch."""
     probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
-    _require_device(image_u8, torch.uint8, "image_u8")
-    image_u8 = image_u8.contiguous()
+    image_u8 = A.to_device(A.image_batch(image_u8, "image_u8", (torch.uint8,)), False, None, "image_u8", _FEATURE).contiguous()
     B, H, W, C = image_u8.shape
     stack = torch.empty(((1 + probes) * B, H, W, C), dtype=torch.uint8, device=image_u8.device)
     N.call("bf_op_risk_probe_u8", N.ptr(image_u8), N.ptr(stack), B, H, W, C, probes, amplitude, seed, N.stream_ptr(image_u8))
@@ -81,18 +59,15 @@ def _launch_sums(affine: bool, image_u8, stack_f32, probes, amplitude, seed) -> 
     """the argument checks and the call of bf_op_risk_sums (float64 [B, C, 1 + K]) or bf_op_risk_sums_affine ([B, C, 2 + 2 K])"""
     probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
     entry, columns = ("bf_op_risk_sums_affine", 2 + 2 * probes) if affine else ("bf_op_risk_sums", 1 + probes)
-    _require_tensor(image_u8, torch.uint8, "image_u8")
-    _require_tensor(stack_f32, torch.float32, "stack_f32")
-    _require_device(image_u8, torch.uint8, "image_u8")
+    A.image_batch(image_u8, "image_u8", (torch.uint8,))
+    A.image_batch(stack_f32, "stack_f32", (torch.float32,))
+    image_u8 = A.to_device(image_u8, False, None, "image_u8", _FEATURE)
     B, H, W, C = image_u8.shape
     if tuple(stack_f32.shape) != ((1 + probes) * B, H, W, C) or stack_f32.device != image_u8.device:
         raise ValueError(f"stack_f32 must be {((1 + probes) * B, H, W, C)} on {image_u8.device} for {probes} probes of a "
                          f"{tuple(image_u8.shape)} batch, got {tuple(stack_f32.shape)} on {stack_f32.device}")
     image_u8, stack_f32 = image_u8.contiguous(), stack_f32.contiguous()
-    nbytes = getattr(N.lib(), entry + "_scratch_bytes")(B, H, W, C, probes)
-    if nbytes < 0:
-        N.check(int(nbytes), None, entry + "_scratch_bytes")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=image_u8.device)
+    scratch, nbytes = N.scratch(entry, image_u8.device, B, H, W, C, probes)
     out = torch.empty((B, C, columns), dtype=torch.float64, device=image_u8.device)
     N.call(entry, N.ptr(image_u8), N.ptr(stack_f32), B, H, W, C, probes, amplitude, seed, N.ptr(scratch), nbytes, N.ptr(out),
            N.stream_ptr(image_u8))
@@ -125,77 +100,30 @@ def risk_from_sums(sums, sigma, height: int, width: int, amplitude: int) -> Risk
     fit = s[:, :, 0] / hw                                             # [B, C]
     div_p = s[:, :, 1:] / a / hw                                      # [B, C, K] divergence per sample, per probe
     div_c = s[:, :, 1:].sum(dim=2) / float(K) / a / hw                # [B, C]
-    mse = (fit - var + 2.0 * var * div_c).sum(dim=1) / float(C)
-    mse_p = (fit.unsqueeze(2) - var.unsqueeze(2) + 2.0 * var.unsqueeze(2) * div_p).sum(dim=1) / float(C)       # [B, K]
+    return _risk_estimate(fit, var, 2.0 * var * div_c, 2.0 * var.unsqueeze(2) * div_p, sg, div_c.sum(dim=1) / float(C), s, was_numpy)
+
+
+def _risk_estimate(fit, var, twice_wdiv_c, twice_wdiv_p, sigma, divergence, sums, was_numpy: bool) -> RiskEstimate:
+    """the tail of both host formulas: fit = R / HW and var, the variance that is subtracted, [B, C]; twice the variance-weighted
+    divergence per sample, over all probes [B, C] and per probe [B, C, K]; sigma [B, C] and the plain divergence [B] as reported"""
+    C, K = fit.shape[1], twice_wdiv_p.shape[2]
+    mse = (fit - var + twice_wdiv_c).sum(dim=1) / float(C)
+    mse_p = (fit.unsqueeze(2) - var.unsqueeze(2) + twice_wdiv_p).sum(dim=1) / float(C)                         # [B, K]
     if K > 1:
         spread = torch.sqrt(((mse_p - mse_p.mean(dim=1, keepdim=True)) ** 2).sum(dim=1) / float(K - 1))
     else:
         spread = torch.full_like(mse, float("nan"))
     psnr = torch.where(mse > 0.0, 10.0 * torch.log10(255.0 ** 2 / mse.clamp_min(1e-300)), torch.full_like(mse, float("inf")))
-    est = RiskEstimate(mse, psnr, sg, torch.sqrt(fit.sum(dim=1) / float(C)), div_c.sum(dim=1) / float(C), spread, s)
+    est = RiskEstimate(mse, psnr, sigma, torch.sqrt(fit.sum(dim=1) / float(C)), divergence, spread, sums)
     return RiskEstimate(*(v.cpu().numpy() for v in est)) if was_numpy else est
-
-
-def _float_callable(module):
-    """the float32 form of `module`: uint8 [B,H,W,C] device tensor -> float32 of the same shape, not rounded"""
-    if isinstance(module, GraphedDenoiserModule):
-        module = module._module                                  # the wrapped module, called directly
-    if isinstance(module, StabilisedDenoiserModule):             # the whole pipeline: transform, module, inverse, not rounded
-        return StabilisedDenoiserModule(module._module, module.noise_level, module.inverse, cast_to_uint8=False,
-                                        min_cells=module.min_cells)
-    if isinstance(module, SelfEnsembleDenoiserModule):
-        return SelfEnsembleDenoiserModule(module._module, module.transforms, cast_to_uint8=False)
-    if isinstance(module, DenoiserModule):
-        inner = DenoiserModule(module.model_hydra, cast_to_uint8=False)
-        inner._deferred = module._deferred                       # one record of pending status words: module.check_status() sees this call
-        return inner
-    if not callable(module):
-        raise ValueError("module must be a DenoiserModule, GraphedDenoiserModule, SelfEnsembleDenoiserModule, "
-                         "StabilisedDenoiserModule or a callable uint8 [B,H,W,C] -> float32 [B,H,W,C]")
-    return module
-
-
-def _checked_noisy(noisy):
-    was_numpy = isinstance(noisy, np.ndarray)
-    t = torch.from_numpy(np.ascontiguousarray(noisy)) if was_numpy else noisy
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4:
-        raise ValueError(f"noisy must be a uint8 [B,H,W,C] tensor or array, got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    if not 1 <= t.shape[3] <= 4 or t.shape[1] < 1 or t.shape[2] < 1:
-        raise ValueError(f"noisy must be [B,H,W,C] with H, W >= 1 and 1..4 channels, got {tuple(t.shape)}")
-    return t, was_numpy
-
-
-def _checked_sigma(sigma, B: int, C: int, what: str = "sigma"):
-    """None, or sigma as a float64 [B, C] host-or-device tensor (a float, [C] or [B, C] was given)"""
-    if sigma is None:
-        return None
-    try:
-        s = torch.as_tensor(sigma).to(torch.float64)
-    except (TypeError, ValueError, RuntimeError):
-        raise ValueError(f"{what} must be None, a float, a [C] or a [B, C] array, got {type(sigma)}") from None
-    if s.dim() == 0:
-        s = s.reshape(1, 1).expand(B, C)
-    elif tuple(s.shape) == (C,):
-        s = s.reshape(1, C).expand(B, C)
-    elif tuple(s.shape) != (B, C):
-        raise ValueError(f"{what} must be a float, [{C}] or [{B}, {C}] for this batch, got {tuple(s.shape)}")
-    if s.numel() and not bool((torch.isfinite(s) & (s >= 0)).all()):
-        raise ValueError(f"{what} must be finite and non-negative")
-    return s.contiguous()
 
 
 def _probed_forward(fn, noisy: torch.Tensor, probes: int, amplitude: int, seed: int) -> torch.Tensor:
     """the float32 result of the float form of the module on the probe stack of a checked, non-empty device batch"""
     stack = risk_probe_stack_u8(noisy, probes, amplitude, seed)
     result = fn(stack)                                           # ONE call on [(1 + K) B, H, W, C]
-    if isinstance(result, torch.Tensor) and result.dtype == torch.uint8:
-        raise ValueError("the module returned uint8: a rounded output cannot carry the finite difference of the probe; "
-                         "pass a module that returns float32 (DenoiserModule(hydra, cast_to_uint8=False))")
-    if not isinstance(result, torch.Tensor) or result.dtype != torch.float32 or result.shape != stack.shape:
-        raise ValueError(f"the module returned {getattr(result, 'dtype', type(result))} {tuple(getattr(result, 'shape', ()))} "
-                         f"for a uint8 {tuple(stack.shape)} batch; float32 of the same shape is needed")
-    return result.to(noisy.device)
+    return A.module_result(result, torch.float32, stack.shape, hint=" (a rounded uint8 output cannot carry the finite difference "
+                           "of the probe: DenoiserModule(hydra, cast_to_uint8=False))").to(noisy.device)
 
 
 def _estimate(fn, noisy: torch.Tensor, sigma, method: str, probes: int, amplitude: int, seed: int) -> RiskEstimate:
@@ -226,22 +154,28 @@ def estimate_risk(module, noisy, sigma=None, method: str = "mad", probes: int = 
     The estimate inherits the arithmetic of the module: D is a difference of two forwards that differ by `amplitude` grey levels,
     so forward rounding enters it relative to that difference (DESIGN.md 7.8 has the measured sizes for the split-f16 and the
     exact-fp32 kernels; on the case measured there the two paths agree on the estimated mse to well below 1 %)."""
-    probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
-    method = _checked_method(method)
-    fn = _float_callable(module)
-    noisy, was_numpy = _checked_noisy(noisy)
-    B, H, W, C = noisy.shape
-    sigma = _checked_sigma(sigma, B, C)
+    A.one_of(method, "method", METHODS)
+    return _framed(module, noisy, (probes, amplitude, seed), lambda K: 1 + K,
+                   lambda B, C: None if sigma is None else A.per_image_channel(sigma, B, C, "sigma"),
+                   lambda fn, y, given, K, a, seed_: _estimate(fn, y, given, method, K, a, seed_))
+
+
+def _framed(module, noisy, probe, columns, levels, run) -> RiskEstimate:
+    """What estimate_risk and estimate_risk_affine share.  The checks, in the order the callers promise: `probe` = (probes,
+    amplitude, seed), the module, the batch, then `levels(B, C)` for the noise level that was given; an empty batch returns empty
+    results ([0, C, columns(probes)] sums) without a device; NumPy is uploaded to the module's device and NumPy comes back, a
+    host tensor is refused.  `run(float form, device batch, levels' result, probes, amplitude, seed)` is the estimate itself."""
+    probes, amplitude, seed = _checked_probe(*probe)
+    fn = float_form(module)
+    noisy, was_numpy = A.host_or_device(noisy, "noisy", (torch.uint8,), allow_empty=True)
+    B, _, _, C = noisy.shape
+    given = levels(B, C)
     if B == 0:
         empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=noisy.device)
-        est = RiskEstimate(empty(0), empty(0), empty(0, C), empty(0), empty(0), empty(0), empty(0, C, 1 + probes))
+        est = RiskEstimate(empty(0), empty(0), empty(0, C), empty(0), empty(0), empty(0), empty(0, C, columns(probes)))
     else:
-        if was_numpy or not noisy.is_cuda:
-            if not was_numpy:
-                raise RuntimeError("noisy must live on the GPU (or be a NumPy array, which is uploaded): the risk kernels have no "
-                                   "CPU execution path")
-            noisy = noisy.to(_module_device(module))
-        est = _estimate(fn, noisy.contiguous(), sigma, method, probes, amplitude, seed)
+        device = A.device_of(module, _FEATURE) if was_numpy else None
+        est = run(fn, A.to_device(noisy, was_numpy, device, "noisy", _FEATURE).contiguous(), given, probes, amplitude, seed)
     return RiskEstimate(*(v.cpu().numpy() for v in est)) if was_numpy else est
 
 
@@ -278,16 +212,8 @@ def risk_from_affine_sums(sums, gain, offset, height: int, width: int, amplitude
     d, dy = s[:, :, 2:2 + K], s[:, :, 2 + K:]
     wdiv_p = (g.unsqueeze(2) * dy + o.unsqueeze(2) * d) / a / hw   # [B, C, K]: sum var_i df_i/dy_i per sample, per probe
     wdiv_c = wdiv_p.sum(dim=2) / float(K)
-    mse = (fit - var + 2.0 * wdiv_c).sum(dim=1) / float(C)
-    mse_p = (fit.unsqueeze(2) - var.unsqueeze(2) + 2.0 * wdiv_p).sum(dim=1) / float(C)                          # [B, K]
-    if K > 1:
-        spread = torch.sqrt(((mse_p - mse_p.mean(dim=1, keepdim=True)) ** 2).sum(dim=1) / float(K - 1))
-    else:
-        spread = torch.full_like(mse, float("nan"))
-    psnr = torch.where(mse > 0.0, 10.0 * torch.log10(255.0 ** 2 / mse.clamp_min(1e-300)), torch.full_like(mse, float("inf")))
     div = d.sum(dim=2).sum(dim=1) / float(K) / a / hw / float(C)
-    est = RiskEstimate(mse, psnr, torch.sqrt(var.clamp_min(0.0)), torch.sqrt(fit.sum(dim=1) / float(C)), div, spread, s)
-    return RiskEstimate(*(v.cpu().numpy() for v in est)) if was_numpy else est
+    return _risk_estimate(fit, var, 2.0 * wdiv_c, 2.0 * wdiv_p, torch.sqrt(var.clamp_min(0.0)), div, s, was_numpy)
 
 
 def estimate_risk_affine(module, noisy, nlf=None, probes: int = 1, amplitude: int = 1, seed: int = 0) -> RiskEstimate:
@@ -310,11 +236,9 @@ def estimate_risk_affine(module, noisy, nlf=None, probes: int = 1, amplitude: in
     v_i E dg/dy_i, this adds 2 gain v_i E d2f_i/dy_i^2 per sample, a second-order term: the estimate is unbiased for every linear f
     and close for a smooth one; the noise is taken as Gaussian (shot noise is Poisson: good above a few tens of electrons) and
     clipping at 0 and 255 is not modelled.  DESIGN.md 7.10 has the measured sizes."""
-    probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
-    fn = _float_callable(module)
-    noisy, was_numpy = _checked_noisy(noisy)
-    B, H, W, C = noisy.shape
-    if nlf is not None:
+    def levels(B, C):
+        if nlf is None:
+            return None
         pair = (nlf.gain, nlf.offset) if isinstance(nlf, NoiseLevelFunction) else nlf
         if not isinstance(pair, (tuple, list)) or len(pair) != 2 or pair[0] is None or pair[1] is None:
             raise ValueError("nlf must be None, a NoiseLevelFunction or a (gain, offset) pair")
@@ -322,23 +246,16 @@ def estimate_risk_affine(module, noisy, nlf=None, probes: int = 1, amplitude: in
             pair = [v if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64) for v in pair]
         except (TypeError, ValueError):
             raise ValueError("gain and offset must each be a float, a [C] or a [B, C] array") from None
-        gain, offset = _checked_sigma(pair[0], B, C, "gain"), _checked_sigma(pair[1], B, C, "offset")
-    if B == 0:
-        empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=noisy.device)
-        est = RiskEstimate(empty(0), empty(0), empty(0, C), empty(0), empty(0), empty(0), empty(0, C, 2 + 2 * probes))
-    else:
-        if was_numpy or not noisy.is_cuda:
-            if not was_numpy:
-                raise RuntimeError("noisy must live on the GPU (or be a NumPy array, which is uploaded): the risk kernels have no "
-                                   "CPU execution path")
-            noisy = noisy.to(_module_device(module))
-        noisy = noisy.contiguous()
-        if nlf is None:
-            fitted = noise_level_function(noisy)
-            gain, offset = fitted.gain, fitted.offset
-        sums = risk_sums_affine(noisy, _probed_forward(fn, noisy, probes, amplitude, seed), probes, amplitude, seed)
-        est = risk_from_affine_sums(sums, gain.to(noisy.device), offset.to(noisy.device), H, W, amplitude)
-    return RiskEstimate(*(v.cpu().numpy() for v in est)) if was_numpy else est
+        return A.per_image_channel(pair[0], B, C, "gain"), A.per_image_channel(pair[1], B, C, "offset")
+
+    def run(fn, y, pair, K, a, seed_):
+        if pair is None:
+            fitted = noise_level_function(y)
+            pair = (fitted.gain, fitted.offset)
+        sums = risk_sums_affine(y, _probed_forward(fn, y, K, a, seed_), K, a, seed_)
+        return risk_from_affine_sums(sums, pair[0].to(y.device), pair[1].to(y.device), y.shape[1], y.shape[2], a)
+
+    return _framed(module, noisy, (probes, amplitude, seed), lambda K: 2 + 2 * K, levels, run)
 
 
 # ---- evaluation without ground truth -------------------------------------------------------------
@@ -356,33 +273,24 @@ def evaluate_blind_risk(module, noisy_batches: Iterable, sigma=None, method: str
     (per sample) and clipped_fraction, the share of saturated input samples -- those violate the assumptions of the estimate.
     Nothing is asserted; the module's deferred f16-range status is checked once at the end."""
     probes, amplitude, seed = _checked_probe(probes, amplitude, seed)
-    method = _checked_method(method)
-    fn = _float_callable(module)
-    if sigma is not None and (isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating))
-                              or not np.isfinite(sigma) or sigma < 0):
-        raise ValueError(f"sigma must be None or a non-negative float, got {sigma!r}")
-    batches = [_check_noisy_batch(b) for b in noisy_batches]
-    if not batches:
-        raise ValueError("no noisy batches to evaluate on")
-    dev = _module_device(module)
+    method = A.one_of(method, "method", METHODS)
+    fn = float_form(module)
+    if sigma is not None:
+        sigma = A.non_negative_float(sigma, "sigma")
+    batches = A.uint8_batches(noisy_batches, "noisy batches", min_hw=3)
+    dev = A.device_of(module, _FEATURE)
     per_image = []                                               # one [5, B] device tensor per batch, rows as _KEYS
     for k, noisy in enumerate(batches):
         noisy = noisy.to(dev).contiguous()
         B, H, W, C = noisy.shape
         stats = noise_statistics(noisy)
-        sg = stats[:, :, 2 if method == "mad" else 1] if sigma is None else _checked_sigma(float(sigma), B, C)
+        sg = stats[:, :, 2 if method == "mad" else 1] if sigma is None else A.per_image_channel(sigma, B, C, "sigma")
         est = _estimate(fn, noisy, sg, method, probes, amplitude, (seed + k) % 2 ** 64)
         sigma_in = torch.sqrt((est.sigma * est.sigma).sum(dim=1) / float(C))
         per_image.append(torch.stack([est.mse, est.psnr, sigma_in, est.divergence, stats[:, :, 3].sum(dim=1) / float(H * W * C)]))
     if hasattr(module, "check_status"):
         module.check_status()                                    # an overflow of the split-f16 kernels is not averaged into a number
-    rows = []
-    with np.errstate(invalid="ignore"):
-        host = [p.cpu().numpy() for p in per_image]
-        for noisy, h in zip(batches, host):
-            rows.append({"shape": [int(v) for v in noisy.shape], "images": int(h.shape[1]), **{k: float(h[i].mean()) for i, k in enumerate(_KEYS)}})
-        every = np.concatenate(host, axis=1)
-        aggregate = {"images": int(every.shape[1]), **{k: float(every[i].mean()) for i, k in enumerate(_KEYS)}}
+    rows, aggregate = summarise(batches, per_image, _KEYS)
     return {"method": method if sigma is None else "given", "probes": probes, "amplitude": amplitude, "images": aggregate["images"],
             "batches": rows, "aggregate": aggregate}
 

@@ -15,10 +15,12 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _native as N
-from .module_denoiser import DenoiserModule
+from .module_denoiser import DenoiserModule, float_form
 
 TRANSFORM_SETS = {"d4": (0, 1, 2, 3, 4, 5, 6, 7), "flips": (0, 2, 4, 6)}
+_FEATURE = "the dihedral transform"
 
 
 def parse_transforms(transforms) -> Tuple[int, ...]:
@@ -46,23 +48,16 @@ def _mask(ks: Sequence[int]) -> int:
     return sum(1 << k for k in ks)
 
 
-def _require_device(t, dtype, what: str):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 4:
-        raise ValueError(f"{what} must be a {dtype} tensor of shape [B,H,W,C], got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} must live on the GPU: the dihedral kernels have no CPU execution path")
+def _device_batch(t, dtype, what: str):
+    return A.to_device(A.image_batch(t, what, (dtype,)), False, None, what, _FEATURE)
 
 
 def dihedral_stack_u8(image_u8: torch.Tensor, members, joint: bool = False) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
     """bf_op_dihedral_stack_u8 on a uint8 device tensor [B,H,W,C] (C = 1 or 3): (even batch [n_even*B,H,W,C] or None, odd batch
     [n_odd*B,W,H,C] or None), member-major in ascending k.  joint=True (H == W only): (all members [n*B,H,W,C], None)."""
     ks = parse_transforms(members)
-    _require_device(image_u8, torch.uint8, "image_u8")
+    image_u8 = _device_batch(image_u8, torch.uint8, "image_u8").contiguous()
     B, H, W, C = image_u8.shape
-    if B < 1 or H < 1 or W < 1:
-        raise ValueError(f"image_u8 must not be empty, got {tuple(image_u8.shape)}")
-    image_u8 = image_u8.contiguous()
     n_odd = sum(k & 1 for k in ks)
     n_even = len(ks) - n_odd
     new = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=image_u8.device)
@@ -95,7 +90,7 @@ def dihedral_merge(even_f32: Optional[torch.Tensor], odd_f32: Optional[torch.Ten
     first = even_f32 if even_f32 is not None else odd_f32
     if first is None:
         raise ValueError("no member batch was given")
-    _require_device(first, torch.float32, "member batch")
+    _device_batch(first, torch.float32, "member batch")
     C = int(first.shape[-1])
     want_even = (len(ks) * B, H, W, C) if joint else (n_even * B, H, W, C) if n_even else None
     want_odd = (n_odd * B, W, H, C) if n_odd and not joint else None
@@ -106,7 +101,7 @@ def dihedral_merge(even_f32: Optional[torch.Tensor], odd_f32: Optional[torch.Ten
             continue
         if t is None:
             raise ValueError(f"{what} is missing for members {list(ks)}")
-        _require_device(t, torch.float32, what)
+        _device_batch(t, torch.float32, what)
         if tuple(t.shape) != want or t.device != first.device:
             raise ValueError(f"{what} must be {want} on {first.device} for members {list(ks)}, got {tuple(t.shape)} on {t.device}")
     even_f32 = None if even_f32 is None else even_f32.contiguous()
@@ -137,8 +132,7 @@ class SelfEnsembleDenoiserModule:
             raise ValueError("module must be a DenoiserModule")
         self._transforms = parse_transforms(transforms)
         self._module, self._cast_to_uint8 = module, bool(cast_to_uint8)
-        self._inner = DenoiserModule(module.model_hydra, cast_to_uint8=False)
-        self._inner._deferred = module._deferred        # one record of pending status words: check_status() below sees the inner calls
+        self._inner = float_form(module)                # shares the status record: check_status() below sees the inner calls
         self.name = module.name
 
     @property
@@ -151,6 +145,10 @@ class SelfEnsembleDenoiserModule:
 
     def check_status(self, wait: bool = True) -> bool:
         return self._module.check_status(wait)
+
+    def float_form(self) -> "SelfEnsembleDenoiserModule":
+        """the same ensemble over the same module, averaged but not rounded"""
+        return SelfEnsembleDenoiserModule(self._module, self._transforms, cast_to_uint8=False)
 
     def __call__(self, image):
         image, was_numpy = self._module._checked_input(image)

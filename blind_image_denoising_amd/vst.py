@@ -16,19 +16,16 @@ from typing import Dict, Iterable
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _native as N
 from .constants import DENOISER_STR
+from .metrics import image_metrics, summarise
+from .module_denoiser import DenoiserModule, float_form
 from .noise_level import NoiseLevelFunction, camera_noise, noise_level_function
 
 GAIN_MAX, OFFSET_MAX = 64.0, 65025.0
 INVERSES = ("exact", "algebraic")
-_NO_GPU = "must live on the GPU: the stabilisation kernels have no CPU execution path"
-
-
-def _checked_inverse(inverse) -> str:
-    if inverse not in INVERSES:
-        raise ValueError(f"inverse must be one of {list(INVERSES)}, got {inverse!r}")
-    return inverse
+_FEATURE = "the stabilisation code"
 
 
 def _checked_noise_level(noise_level):
@@ -57,26 +54,13 @@ def _checked_noise_level(noise_level):
     return out[0], out[1]
 
 
-def _require_images(t, dtype, what: str):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 4:
-        raise ValueError(f"{what} must be a {dtype} tensor of shape [B,H,W,C], got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    B, H, W, C = t.shape
-    if not 1 <= C <= 4 or B < 1 or H < 1 or W < 1:
-        raise ValueError(f"{what} must be a non-empty [B,H,W,C] batch with 1..4 channels, got {tuple(t.shape)}")
-
-
 def _launch_arguments(images, dtype, what: str, noise_level):
     """the argument checks shared by both directions: (contiguous images, gain [B,C], offset [B,C]) on the images' device"""
-    _require_images(images, dtype, what)
+    B, _, _, C = A.image_batch(images, what, (dtype,)).shape
     pair = _checked_noise_level(noise_level)                    # host-given values are refused before the GPU is touched
-    B, _, _, C = images.shape
     for value, name in zip(pair, ("gain", "offset")):
-        shape = tuple(value.shape)
-        if shape not in ((), (C,), (B, C)):
-            raise ValueError(f"{name} must be a float, [{C}] or [{B}, {C}] for this batch, got {shape}")
-    if not images.is_cuda:
-        raise RuntimeError(f"{what} {_NO_GPU}")
+        A.broadcasts_to(value.shape, B, C, name)
+    images = A.to_device(images, False, None, what, _FEATURE)
     gain, offset = (torch.as_tensor(v).to(device=images.device, dtype=torch.float64).expand(B, C).contiguous() for v in pair)
     return images.contiguous(), gain, offset
 
@@ -108,7 +92,7 @@ def unstabilise(stabilised_f32: torch.Tensor, noise_level, inverse: str = "exact
     K1 = sqrt(3/2) / 4, K2 = 11/8, K3 = 5 sqrt(3/2) / 8: the closed form of the exact unbiased inverse of Makitalo & Foi (2013)
     with the terms that diverge as a -> 0 cancelled.  x is clipped to [0, 255]: float32, or uint8 rounded half to even.
     `noise_level` as stabilise_u8 (the same one)."""
-    _checked_inverse(inverse)
+    A.one_of(inverse, "inverse", INVERSES)
     stabilised_f32, gain, offset = _launch_arguments(stabilised_f32, torch.float32, "stabilised_f32", noise_level)
     B, H, W, C = stabilised_f32.shape
     out = torch.empty((B, H, W, C), dtype=torch.uint8 if cast_to_uint8 else torch.float32, device=stabilised_f32.device)
@@ -120,7 +104,7 @@ def unstabilise(stabilised_f32: torch.Tensor, noise_level, inverse: str = "exact
 class StabilisedDenoiserModule:
     """A denoiser run between the variance-stabilising transform and its inverse: uint8 [B,H,W,C] -> uint8 [B,H,W,C] (float32,
     not rounded, with cast_to_uint8=False).  `module`: a DenoiserModule, a SelfEnsembleDenoiserModule, or any callable that maps a
-    uint8 device tensor [N,H,W,C] to float32 of the same shape; its float32 form is what runs (risk._float_callable).
+    uint8 device tensor [N,H,W,C] to float32 of the same shape; its float32 form is what runs (module_denoiser.float_form).
 
     A call is: the argument checks and host-or-device input handling of DenoiserModule; with `noise_level=None` the fit
     noise_level_function(image, min_cells), per image of the batch given, on the device (needs H, W >= 3); stabilise_u8; the float
@@ -134,15 +118,11 @@ class StabilisedDenoiserModule:
     roundings: the wrapper then returns what the module returns to within those."""
 
     def __init__(self, module, noise_level=None, inverse: str = "exact", cast_to_uint8: bool = True, min_cells: int = 64):
-        from .module_denoiser import DenoiserModule
-        from .risk import _float_callable
         if isinstance(module, StabilisedDenoiserModule):
             raise ValueError("module is already stabilised")
-        self._float = _float_callable(module)                    # ValueError for what is not callable
-        self._module, self._inverse, self._cast_to_uint8 = module, _checked_inverse(inverse), bool(cast_to_uint8)
-        if isinstance(min_cells, bool) or not isinstance(min_cells, (int, np.integer)) or min_cells < 1:
-            raise ValueError(f"min_cells must be a positive int, got {min_cells!r}")
-        self._min_cells = int(min_cells)
+        self._float = float_form(module)                         # ValueError for what is not callable
+        self._module, self._inverse, self._cast_to_uint8 = module, A.one_of(inverse, "inverse", INVERSES), bool(cast_to_uint8)
+        self._min_cells = A.int_in(min_cells, "min_cells", 1)
         self._noise_level = None if noise_level is None else _checked_noise_level(noise_level)
         base = module if isinstance(module, DenoiserModule) else getattr(module, "_module", None)
         self._base = base if isinstance(base, DenoiserModule) else None      # whose argument checks and empty output a call uses
@@ -168,26 +148,21 @@ class StabilisedDenoiserModule:
     def check_status(self, wait: bool = True) -> bool:
         return self._module.check_status(wait) if hasattr(self._module, "check_status") else True
 
+    def float_form(self) -> "StabilisedDenoiserModule":
+        """the whole pipeline -- transform, module, inverse -- with the same settings, not rounded"""
+        return StabilisedDenoiserModule(self._module, self._noise_level, self._inverse, cast_to_uint8=False, min_cells=self._min_cells)
+
     def _checked_input(self, image):
         if self._base is not None:
             return self._base._checked_input(image)
-        was_numpy = isinstance(image, np.ndarray)
-        if was_numpy:
-            image = torch.from_numpy(np.ascontiguousarray(image))
-        if not isinstance(image, torch.Tensor) or image.dtype != torch.uint8 or image.dim() != 4:
-            raise ValueError(f"input must be a uint8 tensor or array of shape [B,H,W,C], got "
-                             f"{getattr(image, 'dtype', type(image))} {tuple(getattr(image, 'shape', ()))}")
-        if not 1 <= image.shape[3] <= 4:
-            raise ValueError(f"expected 1..4 channels, got {image.shape[3]}")
-        return image, was_numpy
+        return A.host_or_device(image, "image", (torch.uint8,), min_hw=0, allow_empty=True)      # no base module: any callable
 
     def __call__(self, image):
         image, was_numpy = self._checked_input(image)
         B, H, W, C = image.shape
         if self._noise_level is not None:
             for value, what in zip(self._noise_level, ("gain", "offset")):
-                if tuple(value.shape) not in ((), (C,), (B, C)):
-                    raise ValueError(f"{what} must be a float, [{C}] or [{B}, {C}] for this batch, got {tuple(value.shape)}")
+                A.broadcasts_to(value.shape, B, C, what)
         if B == 0:
             if self._base is not None:
                 return self._base._empty_output(image, was_numpy)
@@ -196,10 +171,8 @@ class StabilisedDenoiserModule:
         if hydra is not None:
             hydra._require_gpu()
             image = image.to(hydra.device)
-        elif was_numpy:
-            if not torch.cuda.is_available():
-                raise RuntimeError(f"image {_NO_GPU}")
-            image = image.cuda()
+        else:
+            image = A.to_device(image, was_numpy, None, "image", _FEATURE)
         image = image.contiguous()
         if self._noise_level is None:
             level = noise_level_function(image, self._min_cells)
@@ -211,10 +184,7 @@ class StabilisedDenoiserModule:
             # host arrays are handed back and an activation left the f16 range: the model now runs the exact-fp32 kernels
             # (check_status switched it); repeat the call
             return self(image.cpu().numpy())
-        if not isinstance(result, torch.Tensor) or result.dtype != torch.float32 or result.shape != image.shape:
-            raise ValueError(f"the module returned {getattr(result, 'dtype', type(result))} {tuple(getattr(result, 'shape', ()))} "
-                             f"for a uint8 {tuple(image.shape)} batch; float32 of the same shape is needed")
-        out = unstabilise(result.to(image.device), level, self._inverse, self._cast_to_uint8)
+        out = unstabilise(A.module_result(result, torch.float32, image.shape).to(image.device), level, self._inverse, self._cast_to_uint8)
         return out.cpu().numpy() if was_numpy else out
 
 
@@ -233,42 +203,28 @@ def evaluate_camera(module, clean_batches: Iterable, gain: float, read_sigma: fl
     batch], "aggregate"}: per entry psnr_*, ssim_*, mae_* for the four arms (means over the images) and fitted_gain /
     fitted_offset (means over images and channels).  Nothing is asserted; the module's deferred f16-range status is checked once
     at the end."""
-    from .metrics import _check_clean_batch, _module_device, image_metrics
-    for value, what in ((gain, "gain"), (read_sigma, "read_sigma")):
-        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not np.isfinite(value) \
-                or value < 0:
-            raise ValueError(f"{what} must be a non-negative float, got {value!r}")
-    known = (float(gain), float(read_sigma) ** 2 + 1.0 / 12.0)
+    gain, read_sigma = A.non_negative_float(gain, "gain"), A.non_negative_float(read_sigma, "read_sigma")
+    known = (gain, read_sigma ** 2 + 1.0 / 12.0)
     arms = {"direct": module,
             "stabilised_known": StabilisedDenoiserModule(module, known),
             "stabilised_fitted": StabilisedDenoiserModule(module, None)}
-    batches = [_check_clean_batch(b) for b in clean_batches]
-    if not batches:
-        raise ValueError("no clean batches to evaluate on")
-    dev = _module_device(module)
+    batches = A.uint8_batches(clean_batches, "clean batches")
+    dev = A.device_of(module, "evaluate_camera")
     per_batch = []                                               # one [14, B] device tensor per batch
     for k, clean in enumerate(batches):
         clean = clean.to(dev).contiguous()
-        noisy = camera_noise(clean, float(gain), float(read_sigma), (int(seed) + k) % 2 ** 64)
+        noisy = camera_noise(clean, gain, read_sigma, (int(seed) + k) % 2 ** 64)
         rows = list(image_metrics(clean, noisy)[:3])
         for name in _ARMS[1:]:
-            denoised = arms[name](noisy)
-            if not isinstance(denoised, torch.Tensor) or denoised.dtype != torch.uint8 or denoised.shape != clean.shape:
-                raise ValueError(f"the module returned {getattr(denoised, 'dtype', type(denoised))} "
-                                 f"{tuple(getattr(denoised, 'shape', ()))} for a uint8 {tuple(clean.shape)} batch")
-            rows += list(image_metrics(clean, denoised)[:3])
+            rows += list(image_metrics(clean, A.module_result(arms[name](noisy), torch.uint8, clean.shape))[:3])
         fit = arms["stabilised_fitted"].last_noise_level
         rows += [fit.gain.mean(dim=1), fit.offset.mean(dim=1)]
         per_batch.append(torch.stack(rows))
     if hasattr(module, "check_status"):
         module.check_status()                                    # an overflow of the split-f16 kernels is not averaged into a number
     keys = [f"{m}_{arm}" for arm in _ARMS for m in _METRICS] + ["fitted_gain", "fitted_offset"]
-    host = [p.cpu().numpy() for p in per_batch]
-    rows = [{"shape": [int(v) for v in b.shape], "images": int(h.shape[1]), **{key: float(h[i].mean()) for i, key in enumerate(keys)}}
-            for b, h in zip(batches, host)]
-    every = np.concatenate(host, axis=1)
-    aggregate = {"images": int(every.shape[1]), **{key: float(every[i].mean()) for i, key in enumerate(keys)}}
-    return {"gain": float(gain), "read_sigma": float(read_sigma), "images": aggregate["images"], "batches": rows,
+    rows, aggregate = summarise(batches, per_batch, keys)
+    return {"gain": gain, "read_sigma": read_sigma, "images": aggregate["images"], "batches": rows,
             "aggregate": aggregate}
 
 

@@ -203,12 +203,12 @@ def test_the_float_form_of_the_wrapper_keeps_its_settings():
     module = _cpu_module()
     ens = bf.SelfEnsembleDenoiserModule(module, "flips")
     st = bf.StabilisedDenoiserModule(ens, ([0.1, 0.2, 0.3], 4.0), inverse="algebraic", min_cells=32)
-    fn = bf.risk._float_callable(st)
+    fn = bf.module_denoiser.float_form(st)
     assert type(fn) is bf.StabilisedDenoiserModule and fn is not st
     assert fn._cast_to_uint8 is False and fn.inverse == "algebraic" and fn.min_cells == 32 and fn.model_hydra is module.model_hydra
     assert fn.noise_level[0].tolist() == [0.1, 0.2, 0.3] and float(fn.noise_level[1]) == 4.0
     assert type(fn._float) is bf.SelfEnsembleDenoiserModule and fn._float.transforms == (0, 2, 4, 6)
-    assert bf.risk._float_callable(bf.StabilisedDenoiserModule(module)).noise_level is None
+    assert bf.module_denoiser.float_form(bf.StabilisedDenoiserModule(module)).noise_level is None
     with pytest.raises(RuntimeError, match="GPU"):
         bf.estimate_risk_affine(st, torch.zeros((1, 8, 8, 3), dtype=torch.uint8), (0.1, 1.0))
 
