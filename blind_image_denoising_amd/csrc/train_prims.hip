@@ -365,11 +365,11 @@ __global__ __launch_bounds__(256) void tp_head_out_bwd_kernel(const float* __res
     }
     for (int o = 0; o < 4; ++o) red[o][threadIdx.x] = acc[o];
     __syncthreads();
-    if ((int)threadIdx.x < hf * co) {
-        const int jj = threadIdx.x / co, o = threadIdx.x % co;
+    for (int e = threadIdx.x; e < hf * co; e += 256) {    // hf * co reaches 512 (hf 128, co 3 or 4): more entries than threads
+        const int jj = e / co, o = e % co;
         float s = 0.f;
         for (int g = 0; g < lanes; ++g) s += red[o][g * hf + jj];
-        partial[(size_t)blockIdx.x * hf * co + threadIdx.x] = s;
+        partial[(size_t)blockIdx.x * hf * co + e] = s;
     }
 }
 

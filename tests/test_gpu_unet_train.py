@@ -157,9 +157,10 @@ V6 = {"decoder_kernel_size": 5, "downsample_type": "conv2d", "gaussian_kernel_si
       "use_laplacian_averaging": True}            # what configs/unet_laplacian_v6.json changes against v5
 
 
-def _setup(depth, width, filters, S, B=2, seed=11, backbone=None):
+def _setup(depth, width, filters, S, B=2, seed=11, backbone=None, denoiser=None):
     cfg = U.canonical_config(depth=depth, width=width, filters=filters)
     cfg["model"]["backbone"].update(backbone or {})
+    cfg["model"]["denoiser"].update(denoiser or {})
     spec = U.UnetLaplacianSpec.from_config(cfg["model"])
     params = U.init_params(spec, seed=seed)
     model = bf.model_builder(cfg["model"], device="cuda").hydra
@@ -202,9 +203,13 @@ def _check_step(spec, params, model, clean, noisy, loss_cfg, dw, depth_scale=Non
 LOSS_V5 = {"hinge": 3.5, "cutoff": 255.0, "mae_multiplier": 1.0, "mse_multiplier": 0.5, "ssim_multiplier": 1.0, "regularization": 0.01}
 
 
-@pytest.mark.parametrize("depth,width,filters,S", [(2, 1, 32, 32), (3, 2, 32, 64)])
-def test_train_step_matches_the_gradient_oracle(depth, width, filters, S):
-    cfg, spec, params, model, clean, noisy = _setup(depth, width, filters, S)
+@pytest.mark.parametrize("depth,width,filters,S,head", [(2, 1, 32, 32, 32), (3, 2, 32, 64, 32), (2, 1, 32, 32, 128)],
+                         ids=["2-1-32-32", "3-2-32-64", "2-1-32-32-head128"])
+def test_train_step_matches_the_gradient_oracle(depth, width, filters, S, head):
+    """head 128: a hidden layer of 128 filters in front of three output channels, 384 entries in the gradient of the last kernel:
+    more than bf_op_head_out_bwd's workgroup has threads"""
+    cfg, spec, params, model, clean, noisy = _setup(depth, width, filters, S, denoiser={"filters": head, "output_channels": 3})
+    assert spec.head_filters == head and spec.out_channels == 3
     _check_step(spec, params, model, clean, noisy, LOSS_V5, [1.0, 0.6, 0.3][:depth])
 
 
