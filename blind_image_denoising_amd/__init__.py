@@ -40,6 +40,8 @@ from .risk import RiskEstimate, risk_probe_stack_u8, risk_sums, estimate_risk, e
 from .risk import risk_sums_affine, risk_from_affine_sums, estimate_risk_affine
 from . import vst
 from .vst import StabilisedDenoiserModule, stabilise_u8, unstabilise, evaluate_camera, format_camera_report
+from . import tiling
+from .tiling import TilePlan, TiledDenoiserModule, tile_plan, tile_split_u8, tile_blend, receptive_radius
 from . import neighbor
 from .neighbor import neighbor_pairs, NeighborPairs, RiskValidator, parse_self_supervised_config
 from . import regularizers
@@ -83,21 +85,30 @@ if pretrained_dir.is_dir():
         }
 
 
-def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None):
+def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None):
     """bfcnn/__init__.py:81-97: a registry name, a model directory (pipeline.json + weights.npz written by
     `save_model`), or a `.keras` archive of a trained unet_laplacian hydra / the directory holding `model_hydra.keras`
     (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]: a
     DenoiserModule, or with `self_ensemble` = "d4", "flips" or a sequence of transform numbers 0..7 that module wrapped in a
-    SelfEnsembleDenoiserModule (the mean over the flips and rotations of the image; self_ensemble.py).  `stabilise` = True or a
-    (gain, offset) pair wraps the result (after any self-ensemble wrapper) in a StabilisedDenoiserModule for camera noise whose
-    variance is gain x + offset: True fits the pair per frame, a pair fixes it (vst.py)."""
+    SelfEnsembleDenoiserModule (the mean over the flips and rotations of the image; self_ensemble.py).  `tiled` = True or a dict
+    of TiledDenoiserModule's settings (tile, overlap, margin, tile_batch) wraps that (after any self-ensemble wrapper) in a
+    TiledDenoiserModule: the frame runs as overlapping tiles of one shape (tiling.py).  `stabilise` = True or a (gain, offset)
+    pair wraps the result (after the self-ensemble and tiling wrappers: the noise fit sees the whole frame) in a
+    StabilisedDenoiserModule for camera noise whose variance is gain x + offset: True fits the pair per frame, a pair fixes it
+    (vst.py)."""
     if stabilise is not None and not isinstance(stabilise, (bool, tuple, list)):
         raise ValueError(f"stabilise must be None, a bool or a (gain, offset) pair, got {stabilise!r}")
     if stabilise is not None and not isinstance(stabilise, bool):
         vst._checked_noise_level(stabilise)                      # a bad pair is refused before anything is loaded
+    if tiled is not None and not isinstance(tiled, (bool, dict)):
+        raise ValueError(f"tiled must be None, a bool or a dict of TiledDenoiserModule settings, got {tiled!r}")
+    if isinstance(tiled, dict) and set(tiled) - {"tile", "overlap", "margin", "tile_batch"}:
+        raise ValueError(f"tiled may set tile, overlap, margin and tile_batch, got {sorted(tiled)}")
     module = _load_module(model_path, device)
     if self_ensemble is not None:
         module = SelfEnsembleDenoiserModule(module, transforms=self_ensemble)
+    if tiled is not None and tiled is not False:
+        module = TiledDenoiserModule(module, **(tiled if isinstance(tiled, dict) else {}))
     if stabilise is None or stabilise is False:
         return module
     return StabilisedDenoiserModule(module, None if stabilise is True else stabilise)

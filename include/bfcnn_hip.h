@@ -684,6 +684,33 @@ int bf_op_dihedral_stack_u8(const uint8_t* src, uint8_t* dst_even, uint8_t* dst_
 int bf_op_dihedral_merge(const float* src_even, const float* src_odd, void* out, int B, int H, int W, int C, int members,
                          int out_u8, void* stream);
 
+/* ---- tiled inference: overlapping tiles of one shape around a denoiser (blind_image_denoising_amd/tiling.py is the host side;
+ * csrc/tiling.hip) ----
+ * Plan per axis (length H, nominal tile T, overlap O, margin M; valid for T >= 1, 0 <= 2 M <= O <= T / 2):
+ *   tile extent t = min(T, H); tile count n = 1 if H <= T, else ceil((H - O) / (T - O)); origins y_i = (i (H - t)) / (n - 1)
+ *   (integer division; y_0 = 0 for n == 1).  The origins increase strictly, the first is 0, the last tile ends at H, neighbours
+ *   overlap by at least O.  All tiles of a plan have the shape [t_h, t_w].
+ * Integer weight of tile i at its local coordinate u in [0, t), with R = O - 2 M:
+ *   lead(u) = R + 1 if y_i == 0, else clamp(u - M + 1, 0, R + 1);  trail(u) = R + 1 if y_i + t == H, else clamp(t - M - u, 0, R + 1);
+ *   a_i(u) = min(lead, trail).  A tile's weight at a pixel is a_iy(y - y_iy) a_ix(x - x_ix): the outer M pixels of every interior
+ *   tile edge weigh nothing, edges on the image border lose nothing, and every pixel has a positive weight from 1 to 3 tiles per axis.
+ * Tile order: (b, iy, ix) row-major, N = B ny nx tiles.  `overlap` and `margin` hold for both axes.
+ * Blend, per output sample, in fp64: num = sum w (double) f, den = sum w over the tiles with w > 0 in ascending tile order,
+ *   q = num / den (correctly rounded); float32 result (float) q; uint8 result rintf(fminf(fmaxf((float) q, 0), 255)), half to even.
+ *   The weights are small integers, each product is exact in fp64: the result is reproducible bit for bit.
+ * C is 1 or 3 (BF_EUNSUPPORTED otherwise, and for frames beyond the kernels' 32-bit plan arithmetic: (n - 1) H >= 2^31 on an axis,
+ * B H >= 2^31, a tile of 2^31 bytes, W > 65535 * 256).  BF_EINVAL for NULL or aliased pointers, sizes below 1, an invalid plan
+ * or a tile range outside [0, N).  Scalars only: one launch each, no upload, no allocation, no synchronisation, graph-capturable.
+ * Every element offset is 64-bit.
+ *
+ * bf_op_tile_split_u8: tiles [first, first + count) of the tile order of src[B,H,W,C] -> dst[count, t_h, t_w, C].
+ * bf_op_tile_blend: tiles[N, t_h, t_w, C] float32 -> out[B,H,W,C], float32 (out_is_u8 == 0) or uint8; a gather, one thread per
+ *   output pixel, no atomics. */
+int bf_op_tile_split_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int tile_h, int tile_w, int overlap,
+                        int64_t first, int64_t count, void* stream);
+int bf_op_tile_blend(const float* tiles, void* out, int out_is_u8, int B, int H, int W, int C, int tile_h, int tile_w,
+                     int overlap, int margin, void* stream);
+
 /* ---- risk estimation without a clean image: Stein's unbiased risk estimate around a denoiser (blind_image_denoising_amd/risk.py
  * is the host side; csrc/risk.hip).  For y = x + n, n ~ N(0, sigma^2): E |f(y) - x|^2 / N = E[ |f(y) - y|^2 / N - sigma^2 +
  * (2 sigma^2 / N) div f(y) ], div f(y) ~ s . (f(y + a s) - f(y)) / a for a random sign vector s (Ramani, Blu, Unser 2008).
