@@ -42,6 +42,8 @@ from . import vst
 from .vst import StabilisedDenoiserModule, stabilise_u8, unstabilise, evaluate_camera, format_camera_report
 from . import tiling
 from .tiling import TilePlan, TiledDenoiserModule, tile_plan, tile_split_u8, tile_blend, receptive_radius
+from . import degrade
+from .degrade import Degradations, degrade_jpeg, degrade_blur, degrade_pointwise, gaussian_taps
 from . import neighbor
 from .neighbor import neighbor_pairs, NeighborPairs, RiskValidator, parse_self_supervised_config
 from . import regularizers

@@ -192,6 +192,10 @@ SIGNATURES = {
     "bf_op_risk_sums_affine_scratch_bytes": (_I64, [_I, _I, _I, _I, _I]),
     "bf_op_risk_sums_affine": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _P, _I64, _P, _P]),
     "bf_op_neighbor_pairs": (_I, [_P, _I, _P, _F, _P, _P, _I, _I, _I, _I, C.c_uint64, _P]),
+    "bf_op_degrade_jpeg_scratch_bytes": (_I64, [_I, _I, _I, _I, _I]),
+    "bf_op_degrade_jpeg": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I64, _P]),
+    "bf_op_degrade_blur": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "bf_op_degrade_pointwise": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, C.c_uint64, _P]),
     "bf_set_option": (_I, [_P, C.c_char_p, _I]),
     "bf_get_timing": (_I, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "bf_get_block_kernel": (C.c_char_p, [_P, C.POINTER(C.c_int)]),

@@ -24,13 +24,18 @@ from .custom_logger import logger
 def noise_augment(input_batch: torch.Tensor, flip_left_right: bool = False, flip_up_down: bool = False,
                   mult_std: float = 0.0, add_std: float = 0.0, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """one bf_noise_augment call: (round(flip(x)), round(round(flip(x)) * tn(1, mult_std) + tn(0, add_std)))."""
+    return _noise_augment(input_batch, flip_left_right, flip_up_down, mult_std, add_std, seed, True)
+
+
+def _noise_augment(input_batch, flip_left_right, flip_up_down, mult_std, add_std, seed, want_clean):
+    """noise_augment; without `want_clean` the clean output is neither allocated nor written (None comes back in its place)"""
     if input_batch.dim() != 4:
         raise ValueError(f"expected a [B,H,W,C] batch, got {tuple(input_batch.shape)}")
     if not input_batch.is_cuda:
         raise RuntimeError("noise_augment runs on the MI355X: the engine has no CPU execution path")
     x = input_batch.to(torch.float32).contiguous()
     B, H, W, C = x.shape
-    clean, noisy = torch.empty_like(x), torch.empty_like(x)
+    clean, noisy = torch.empty_like(x) if want_clean else None, torch.empty_like(x)
     flip = (1 if flip_left_right else 0) | (2 if flip_up_down else 0)
     N.check(N.lib().bf_noise_augment(N.ptr(x), N.ptr(clean), N.ptr(noisy), B, H, W, C, flip, float(mult_std), float(add_std),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, N.stream_ptr(x)), None, "bf_noise_augment")
@@ -39,7 +44,12 @@ def noise_augment(input_batch: torch.Tensor, flip_left_right: bool = False, flip
 
 class PrepareData:
     """`prepare_data_fn` (bfcnn/dataset.py:126-239) built from the same `dataset` config section
-    (dataset.py:92-121): random_left_right, random_up_down, additional_noise, multiplicative_noise."""
+    (dataset.py:92-121): random_left_right, random_up_down, additional_noise, multiplicative_noise.
+
+    An optional `degradations` section (degrade.py: blur, quantization, jpeg, drop) adds blind degradations of the NOISY output,
+    drawn per image from a generator of their own; without it the batches are exactly what they were.  The stages, in order:
+    flip and round; blur; multiplicative and additive noise, then round; clip and quantise; JPEG; drop.  The clean output is never
+    degraded."""
 
     def __init__(self, config: Dict, seed: Optional[int] = None):
         self.use_left_right = bool(config.get("random_left_right", False))
@@ -60,6 +70,10 @@ class PrepareData:
         if self.ignored:
             logger.info(f"dataset options without effect in prepare_data_fn (as in the reference): {self.ignored}")
         self.rng = np.random.default_rng(seed)
+        self.degradations = None
+        if config.get("degradations") is not None:
+            from .degrade import Degradations
+            self.degradations = Degradations(config["degradations"], seed)
 
     def draw(self) -> Dict:
         """the per-batch scalars, in the order the reference draws them (dataset.py:141-142, 170-187)."""
@@ -74,7 +88,24 @@ class PrepareData:
                 "seed": int(r.integers(0, 2 ** 63 - 1))}
 
     def __call__(self, input_batch: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        return noise_augment(input_batch, **self.draw())
+        d = self.draw()
+        if self.degradations is None:
+            return noise_augment(input_batch, **d)
+        return self.degrade(input_batch, d, self.degradations.draw(int(input_batch.shape[0])))
+
+    def degrade(self, input_batch: torch.Tensor, d: Dict, params: Dict) -> Tuple[torch.Tensor, torch.Tensor]:
+        """the stages for the per-batch scalars `d` (draw) and the per-image parameters `params` (Degradations.draw): a launch per
+        stage that fires for some image, none for a stage that does not.  With a blur the noise kernel runs twice: once for the
+        flips and the rounding, once on the blurred batch with the flips off and the same seed -- its stream is indexed by the
+        output element, so the noise field is the one the batch would get without the blur"""
+        clean, noisy = _noise_augment(input_batch, d["flip_left_right"], d["flip_up_down"], 0.0, 0.0, d["seed"], True) \
+            if (params["sigma"] > 0).any() else noise_augment(input_batch, **d)
+        blurred = self.degradations.blur(clean, params)
+        if blurred is not None:
+            noisy = blurred
+            if d["mult_std"] > 0.0 or d["add_std"] > 0.0:
+                _, noisy = _noise_augment(blurred, False, False, d["mult_std"], d["add_std"], d["seed"], False)
+        return clean, self.degradations.apply(noisy, params, d["seed"])
 
 
 DatasetResults = namedtuple("DatasetResults", ["config", "batch_size", "input_shape", "training", "testing"])      # dataset.py:27-35

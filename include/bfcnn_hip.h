@@ -761,6 +761,46 @@ int bf_op_risk_sums_affine(const uint8_t* y, const float* f, int B, int H, int W
 int bf_op_neighbor_pairs(const void* y, int y_is_u8, const float* f, float lambda, float* input, float* target, int B, int H, int W,
                          int C, uint64_t seed, void* stream);
 
+/* ---- blind degradations for training: JPEG, blur, quantisation, drop-out (blind_image_denoising_amd/degrade.py is the host side;
+ * csrc/degrade.hip) ----
+ * Common: src is [B,H,W,C], uint8 when src_is_u8 != 0, else float32; a sample's 8-bit code is p = clip(rint(x), 0, 255) (half to
+ * even; the identity on the integer-valued samples bf_noise_augment writes).  Everything after that is integer arithmetic with
+ * arithmetic (floor) shifts, every accumulator fits int32 (uint32 for the vertical blur sum), so the float32 outputs -- integers
+ * in [0, 255] -- are the same bits for every launch geometry and base alignment.  Per-image parameters are DEVICE int32 arrays
+ * of B entries; one launch covers the batch.  BF_EINVAL for NULL or aliased pointers, sizes below 1, C outside 1..4;
+ * BF_EUNSUPPORTED for B > 65535 or an axis beyond the grid limits.  No allocation, no synchronisation: graph-capturable.
+ *
+ * bf_op_degrade_jpeg: encode / decode round trip without entropy coding.  C is 1 or 3 (else BF_EINVAL); quality[b] in 1..100, or 0
+ * for an image of the batch that is not encoded (its codes come out: what lets one launch serve a batch of which some images fire);
+ * subsampling 444 or 420 (C == 1: a Y plane with the luminance table, subsampling has no effect).
+ *   padding by edge replication to a multiple of 8 (16 for 420); every step works on the padded planes, the crop comes last
+ *   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16;  Cb = (-11058 R - 21710 G + 32768 B + (128 << 16) + 32767) >> 16;
+ *   Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16;  420 chroma: (a + b + c + d + 2) >> 2 over each 2 x 2 cell
+ *   tables: Annex K base tables, s = 5000 / q for q < 50 else 200 - 2 q, tbl = clip((base s + 50) / 100, 1, 255)
+ *   DCT of p - 128 with T[u][x] = rint(8192 c(u) / 2 cos((2 x + 1) u pi / 16)):  a[y][u] = (sum_x T[u][x] p[y][x] + 512) >> 10,
+ *   c8[v][u] = (sum_y T[v][y] a[y][u] + 4096) >> 13 (8 x the coefficient);  k = sign(c8) ((|c8| + 4 tbl) / (8 tbl)), c = k tbl
+ *   inverse: a[y][u] = (sum_v T[v][y] c[v][u] + 512) >> 10,  p[y][x] = clip(((sum_u T[u][x] a[y][u] + 32768) >> 16) + 128, 0, 255)
+ *   420 upsampling, triangle filter on the padded half-size plane with replicated edges: rows v_even = 3 c[i] + c[i-1],
+ *   v_odd = 3 c[i] + c[i+1];  columns o_even = (3 v[j] + v[j-1] + 8) >> 4, o_odd = (3 v[j] + v[j+1] + 7) >> 4
+ *   cb = Cb - 128, cr = Cr - 128:  R = Y + ((91881 cr + 32768) >> 16),  G = Y + ((-22553 cb - 46802 cr + 32768) >> 16),
+ *   B = Y + ((116130 cb + 32768) >> 16), clipped.
+ *   420 makes two launches through planar uint8 scratch of bf_op_degrade_jpeg_scratch_bytes bytes (0 for 444 and C == 1);
+ *   BF_EWORKSPACE when it is too small.
+ * bf_op_degrade_blur: separable Gaussian with integer taps.  taps = int32 [B][25], the first 2 radius[b] + 1 of a row used,
+ *   radius[b] in 0..12, a row's taps non-negative with sum 65536 (degrade.gaussian_taps builds them; radius 0 with the tap 65536 is
+ *   the identity).  Borders clamp.  h = sum w p (< 2^24), h8 = (h + 128) >> 8; v = sum w h8 (< 2^32, unsigned);
+ *   out = (v + 2^23) >> 24.  One launch, tiled through LDS with the halo.
+ * bf_op_degrade_pointwise: out = min(255, ((p + step / 2) / step) step), step[b] in 1..255; then, with threshold[b] = t =
+ *   floor(rate 2^24) > 0, pixel i = y W + x of image b is dropped (all channels 0) when word 0 of philox4x32_10(counter =
+ *   (lo32 i, hi32 i, b, 4), key = (lo32 seed, hi32 seed)) >> 8 is below t.  mask: uint8 [B,H,W], 1 = dropped, or NULL. */
+int64_t bf_op_degrade_jpeg_scratch_bytes(int B, int H, int W, int C, int subsampling);
+int bf_op_degrade_jpeg(const void* src, int src_is_u8, float* dst, int B, int H, int W, int C, const int32_t* quality,
+                       int subsampling, void* scratch, int64_t scratch_bytes, void* stream);
+int bf_op_degrade_blur(const void* src, int src_is_u8, float* dst, int B, int H, int W, int C, const int32_t* taps,
+                       const int32_t* radius, void* stream);
+int bf_op_degrade_pointwise(const void* src, int src_is_u8, float* dst, uint8_t* mask, int B, int H, int W, int C,
+                            const int32_t* step, const int32_t* threshold, uint64_t seed, void* stream);
+
 /* ---- options and diagnostics (not part of the drop-in surface; used by tests/) ------------- */
 
 /* Inference forwards keep a status word in the LAST 2048 bytes of the workspace they are given (ws + ws_bytes - 2048,
