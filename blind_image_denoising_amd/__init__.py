@@ -42,6 +42,10 @@ from . import vst
 from .vst import StabilisedDenoiserModule, stabilise_u8, unstabilise, evaluate_camera, format_camera_report
 from . import tiling
 from .tiling import TilePlan, TiledDenoiserModule, tile_plan, tile_split_u8, tile_blend, receptive_radius
+from . import pixel_shuffle
+from .pixel_shuffle import (NoiseCorrelation, PixelShuffleDenoiserModule, noise_correlation, noise_correlation_statistics,
+                            pd_split_u8, pd_merge, pd_replace_u8, pd_mean)
+from .pixel_shuffle import parse_setting as pixel_shuffle_settings
 from . import degrade
 from .degrade import Degradations, degrade_jpeg, degrade_blur, degrade_pointwise, gaussian_taps
 from . import neighbor
@@ -87,15 +91,18 @@ if pretrained_dir.is_dir():
         }
 
 
-def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None):
+def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None, pixel_shuffle=None):
     """bfcnn/__init__.py:81-97: a registry name, a model directory (pipeline.json + weights.npz written by
     `save_model`), or a `.keras` archive of a trained unet_laplacian hydra / the directory holding `model_hydra.keras`
     (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]: a
     DenoiserModule, or with `self_ensemble` = "d4", "flips" or a sequence of transform numbers 0..7 that module wrapped in a
     SelfEnsembleDenoiserModule (the mean over the flips and rotations of the image; self_ensemble.py).  `tiled` = True or a dict
     of TiledDenoiserModule's settings (tile, overlap, margin, tile_batch) wraps that (after any self-ensemble wrapper) in a
-    TiledDenoiserModule: the frame runs as overlapping tiles of one shape (tiling.py).  `stabilise` = True or a (gain, offset)
-    pair wraps the result (after the self-ensemble and tiling wrappers: the noise fit sees the whole frame) in a
+    TiledDenoiserModule: the frame runs as overlapping tiles of one shape (tiling.py).  `pixel_shuffle` = a stride, "auto" (True
+    means "auto") or a dict of PixelShuffleDenoiserModule's settings (stride, max_stride, threshold, refine, replace, seed) wraps
+    that (after the self-ensemble and tiling wrappers) in a PixelShuffleDenoiserModule for noise that is correlated over a few
+    pixels: the sub-images of every s-th pixel run as one batch (pixel_shuffle.py).  `stabilise` = True or a (gain, offset)
+    pair wraps the result (after every other wrapper: the noise fit sees the whole frame) in a
     StabilisedDenoiserModule for camera noise whose variance is gain x + offset: True fits the pair per frame, a pair fixes it
     (vst.py)."""
     if stabilise is not None and not isinstance(stabilise, (bool, tuple, list)):
@@ -106,11 +113,14 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
         raise ValueError(f"tiled must be None, a bool or a dict of TiledDenoiserModule settings, got {tiled!r}")
     if isinstance(tiled, dict) and set(tiled) - {"tile", "overlap", "margin", "tile_batch"}:
         raise ValueError(f"tiled may set tile, overlap, margin and tile_batch, got {sorted(tiled)}")
+    shuffle = pixel_shuffle_settings(pixel_shuffle)              # a bad setting is refused before anything is loaded
     module = _load_module(model_path, device)
     if self_ensemble is not None:
         module = SelfEnsembleDenoiserModule(module, transforms=self_ensemble)
     if tiled is not None and tiled is not False:
         module = TiledDenoiserModule(module, **(tiled if isinstance(tiled, dict) else {}))
+    if shuffle is not None:
+        module = PixelShuffleDenoiserModule(module, **shuffle)
     if stabilise is None or stabilise is False:
         return module
     return StabilisedDenoiserModule(module, None if stabilise is True else stabilise)

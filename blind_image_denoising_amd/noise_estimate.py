@@ -5,7 +5,8 @@ No-reference noise estimation on the device, and the evaluation of a blind denoi
 [B,H,W,C] batch that leaves, per image and channel, the Immerkaer sum S = sum |image (*) [[1,-2,1],[-2,4,-2],[1,-2,1]]| and
 sigma_fast = sqrt(pi/2) / 6 * S / ((H-2)(W-2)) (Immerkaer, "Fast noise variance estimation", 1996), sigma_mad = the median of
 the finest diagonal Haar band / 0.6745 (Donoho's MAD rule, from an exact histogram; uint8 only) and the number of saturated
-samples (0 or 255; uint8 only).  Both estimators assume additive noise that is white at the pixel scale; saturation biases
+samples (0 or 255; uint8 only).  Both estimators assume additive noise that is white at the pixel scale (correlated noise reads
+low: pixel_shuffle.noise_correlation measures how far it reaches and the level beyond); saturation biases
 both low, which is why the clipped fraction is reported next to them.  Nothing synchronises; there is no CPU execution path.
 
 `evaluate_blind(module, noisy_batches)` answers, for photographs that are already noisy: how noisy is the frame (sigma_in), how
