@@ -46,6 +46,9 @@ from . import pixel_shuffle
 from .pixel_shuffle import (NoiseCorrelation, PixelShuffleDenoiserModule, noise_correlation, noise_correlation_statistics,
                             pd_split_u8, pd_merge, pd_replace_u8, pd_mean)
 from .pixel_shuffle import parse_setting as pixel_shuffle_settings
+from . import burst
+from .burst import BurstDenoiserModule, burst_pyramid, burst_align, burst_thresholds, burst_merge
+from .burst import parse_setting as burst_settings
 from . import degrade
 from .degrade import Degradations, degrade_jpeg, degrade_blur, degrade_pointwise, gaussian_taps
 from . import neighbor
@@ -91,7 +94,7 @@ if pretrained_dir.is_dir():
         }
 
 
-def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None, pixel_shuffle=None):
+def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None, pixel_shuffle=None, burst=None):
     """bfcnn/__init__.py:81-97: a registry name, a model directory (pipeline.json + weights.npz written by
     `save_model`), or a `.keras` archive of a trained unet_laplacian hydra / the directory holding `model_hydra.keras`
     (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]: a
@@ -104,7 +107,9 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
     pixels: the sub-images of every s-th pixel run as one batch (pixel_shuffle.py).  `stabilise` = True or a (gain, offset)
     pair wraps the result (after every other wrapper: the noise fit sees the whole frame) in a
     StabilisedDenoiserModule for camera noise whose variance is gain x + offset: True fits the pair per frame, a pair fixes it
-    (vst.py)."""
+    (vst.py).  `burst` = True or a dict of BurstDenoiserModule's settings (reference, levels, search, sigma, k) wraps the result,
+    outermost, in a BurstDenoiserModule: the callable then takes uint8 [B,T,H,W,C] bursts, aligns and merges their frames and
+    denoises the merged frame (burst.py)."""
     if stabilise is not None and not isinstance(stabilise, (bool, tuple, list)):
         raise ValueError(f"stabilise must be None, a bool or a (gain, offset) pair, got {stabilise!r}")
     if stabilise is not None and not isinstance(stabilise, bool):
@@ -114,6 +119,7 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
     if isinstance(tiled, dict) and set(tiled) - {"tile", "overlap", "margin", "tile_batch"}:
         raise ValueError(f"tiled may set tile, overlap, margin and tile_batch, got {sorted(tiled)}")
     shuffle = pixel_shuffle_settings(pixel_shuffle)              # a bad setting is refused before anything is loaded
+    merge = burst_settings(burst)
     module = _load_module(model_path, device)
     if self_ensemble is not None:
         module = SelfEnsembleDenoiserModule(module, transforms=self_ensemble)
@@ -121,9 +127,9 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
         module = TiledDenoiserModule(module, **(tiled if isinstance(tiled, dict) else {}))
     if shuffle is not None:
         module = PixelShuffleDenoiserModule(module, **shuffle)
-    if stabilise is None or stabilise is False:
-        return module
-    return StabilisedDenoiserModule(module, None if stabilise is True else stabilise)
+    if stabilise is not None and stabilise is not False:
+        module = StabilisedDenoiserModule(module, None if stabilise is True else stabilise)
+    return module if merge is None else BurstDenoiserModule(module, **merge)
 
 
 def _load_module(model_path: str, device=None) -> DenoiserModule:

@@ -745,6 +745,39 @@ int bf_op_pd_replace_u8(const uint8_t* base, const uint8_t* noisy, uint8_t* dst,
                         unsigned threshold, uint64_t seed, void* stream);
 int bf_op_pd_mean(const float* src, void* out, int out_is_u8, int B, int H, int W, int C, int copies, void* stream);
 
+/* ---- burst merge: block-matching alignment of T frames to one of them and the robust temporal merge along the alignment
+ * (blind_image_denoising_amd/burst.py is the host side; csrc/burst.hip) ----
+ * frames = uint8 [B,T,H,W,C], T in 1..16, C in 1..4, `ref` in 0..T-1 the reference frame; clamp(p) clips a coordinate to the frame.
+ * Everything is integer arithmetic up to the one division of the merge.  Scalars only: no upload, no allocation, no
+ * synchronisation, graph-capturable.  BF_EINVAL for NULL, a bad shape or setting, short or misaligned buffers, and frames beyond
+ * the kernels' 32-bit arithmetic (H W C > 2^29 - 1, B T (H W / 16 + H + W + 1) > 2^29 - 1).
+ *
+ * Luma pyramid, `levels` = K in 1..4: L_0 = (2 sum_c x_c + C) / (2 C) (integer division), uint8; level k + 1 is ceil(H_k / 2) x
+ *   ceil(W_k / 2), each value (the sum of the 2 x 2 cell at (2 y, 2 x), coordinates clamped, + 2) >> 2.
+ * Alignment: tiles of 16 x 16 at every level, the grid of level k is gy_k x gx_k = ceil(H_k / 16) x ceil(W_k / 16), edge tiles are
+ *   cut by the frame.  Coarsest level first; tile (i, j) of level k starts from d0 = 2 d_{k+1}[min(i >> 1, gy_{k+1} - 1),
+ *   min(j >> 1, gx_{k+1} - 1)] (0 at the coarsest level) and takes, among d = d0 + (u, v), u, v in -R..R (`search` = R in 1..7),
+ *   the one with the smallest key (cost, u u + v v, u, v), compared lexicographically,
+ *   cost(d) = sum over the tile's pixels p of |L_ref(p) - L_alt(clamp(p + d))|.
+ *   field_out = int32 [B,T,gy_0,gx_0,2] as (dy, dx), zero for t == ref.  The reach is R (2^K - 1) pixels.
+ * Scratch (bf_burst_align_scratch_bytes bytes, 16-byte aligned), every part starting on a multiple of 16 bytes and padded to one:
+ *   uint8 [B T, H_k, W_k] luma for k = 0..K-1, then int32 [B T, gy_k, gx_k, 2] fields for k = 1..K-1.  Both are left behind
+ *   for the caller to read.
+ *
+ * Merge: pixel p lies in tile (p_y / 16, p_x / 16) whose displacement in frame t is d_t = field[b,t,.,.].
+ *   D_t = sum over q in the 5 x 5 window around p (q clamped first), over the channels, of (alt_t(clamp(q + d_t)) - ref(q))^2;
+ *   thresholds = int64 [B,2] = (lo, hi) per image, 0 <= lo < hi < 2^54;
+ *   w_t = 256 if D_t <= lo, 0 if D_t >= hi, else ((hi - D_t) 256) / (hi - lo) (integer division); w_ref = 256;
+ *   num_c = sum_t w_t alt_t,c(clamp(p + d_t)), den = sum_t w_t, sq = sum_t w_t^2;
+ *   out [B,H,W,C] = (float) ((double) num_c / (double) den): one correctly rounded division, one cast (out_is_u8 == 0), or that
+ *   float32 value rounded half to even to uint8.  counts_or_null = int32 [B,H,W,2] = (den, sq): the noise of the merged pixel is
+ *   sigma sqrt(sq) / den.  A displacement is any int32 (clamp saturates).  `out` must not alias `frames`. */
+int64_t bf_burst_align_scratch_bytes(int B, int T, int H, int W, int C, int levels);
+int bf_burst_align(const uint8_t* frames, int B, int T, int H, int W, int C, int ref, int levels, int search, void* scratch,
+                   int64_t scratch_bytes, int* field_out, void* stream);
+int bf_op_burst_merge(const uint8_t* frames, const int* field, const int64_t* thresholds, int B, int T, int H, int W, int C, int ref,
+                      void* out, int out_is_u8, int* counts_or_null, void* stream);
+
 /* ---- risk estimation without a clean image: Stein's unbiased risk estimate around a denoiser (blind_image_denoising_amd/risk.py
  * is the host side; csrc/risk.hip).  For y = x + n, n ~ N(0, sigma^2): E |f(y) - x|^2 / N = E[ |f(y) - y|^2 / N - sigma^2 +
  * (2 sigma^2 / N) div f(y) ], div f(y) ~ s . (f(y + a s) - f(y)) / a for a random sign vector s (Ramani, Blu, Unser 2008).
