@@ -972,12 +972,17 @@ __global__ __launch_bounds__(256) void uo_dwconv_ln_rows_kernel(const float* __r
     }
 }
 
+// k = 7 (C in {32, 64, 128}): dwconv7_ln.hip -- 49 tap vectors per lane do not fit beside the accumulators, they live in LDS there
+int bf_dwconv7_ln(const float* in, float* out, const float* w, const float* ln_gamma, int B, int H, int W, int C, float eps, int act,
+                  float alpha, hipStream_t s);
+
 extern "C" int bf_op_dwconv_ln(const float* in, float* out, const float* w, const float* ln_gamma, int B, int H, int W, int C, int k,
                                float eps, int act, float alpha, void* stream)
 {
     if (!in || !out || B <= 0 || H <= 0 || W <= 0 || (k > 0 && !w)) return BF_EINVAL;
     if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)w | (uintptr_t)ln_gamma) % 16) return BF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
+    if (k == 7) return bf_dwconv7_ln(in, out, w, ln_gamma, B, H, W, C, eps, act, alpha, s);
     const int64_t npix = (int64_t)B * H * W;
     bool ok = false;
     constexpr int RROWS = 32;          // rows per workgroup: k - 1 halo rows are re-read and re-multiplied per strip

@@ -498,7 +498,7 @@ class _SubModelView:
 
 
 def _build_hydra(config: Dict, device=None, strict_snapshot: bool = False, seed: Optional[int] = None):
-    """backbone type -> model class: unet_laplacian; unet; the 16-filter 3x3 resnet family (fused engine, trainable); any other
+    """backbone type -> model class: unet_laplacian; unet; convnext; the 16-filter 3x3 resnet family (fused engine, trainable); any other
     resnet the operator library covers (per-position kernels / filters, depthwise multipliers, groups; inference)."""
     btype = str(config[BACKBONE_STR].get(TYPE_STR, "")).strip().lower()
     if btype == "unet_laplacian":
@@ -507,6 +507,9 @@ def _build_hydra(config: Dict, device=None, strict_snapshot: bool = False, seed:
     if btype == "unet":
         from .unet_backbone import UnetHydra
         return UnetHydra(config, device=device, seed=seed)
+    if btype == "convnext":
+        from .convnext_backbone import ConvnextHydra
+        return ConvnextHydra(config, device=device, seed=seed)
     try:
         return HydraModel(config, device=device, strict_snapshot=strict_snapshot, seed=seed)
     except NotImplementedError as first:

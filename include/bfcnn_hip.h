@@ -391,7 +391,10 @@ int bf_op_convnext_block_h3(const float* x, float* out, const float* dw, int k, 
  * 0 = the single-role one, 3 = two workgroups per CU, 4 = 2 with two consumer waves per SIMD (k = 3 only; k = 5 runs 2). */
 int bf_op_set_variant(const char* key, int value);
 /* DepthwiseConv2D k x k (SAME, zero pad; w [k][k][C]; k = 0: none) -> LayerNormalization(center=False, epsilon) * gamma
- * (ln_gamma NULL: none) -> activation   (custom_layers.py:979-988; backbone_unet_laplacian.py:355-360). */
+ * (ln_gamma NULL: none) -> activation   (custom_layers.py:979-988; backbone_unet_laplacian.py:355-360; the first layer of the
+ * ConvNeXt block, backbone_convnext.py:108-113).  fp32 NHWC, out != in.  Built: k in {0, 1, 3, 5} for channels in {32, 64, 128,
+ * 256}; k = 7 for channels in {32, 64, 128} (its own kernel, dwconv7_ln.hip: the 49 tap vectors in LDS, two columns per lane);
+ * every other (channels, k) returns BF_EUNSUPPORTED.  H, W smaller than k are fine.  Deterministic: a fixed summation order. */
 int bf_op_dwconv_ln(const float* in, float* out, const float* w, const float* ln_gamma, int batch, int height, int width,
                     int channels, int k, float eps, int act, float alpha, void* stream);
 /* Laplacian split between levels (backbone_unet_laplacian.py:366-386): smooth = AveragePooling2D(k, strides 1, same) or,
