@@ -49,6 +49,9 @@ from .pixel_shuffle import parse_setting as pixel_shuffle_settings
 from . import burst
 from .burst import BurstDenoiserModule, burst_pyramid, burst_align, burst_thresholds, burst_merge
 from .burst import parse_setting as burst_settings
+from . import nlm as _nlm
+from .nlm import NlmDenoiserModule, nlm, nlm_params, nlm_table, nlm_tune
+from .nlm import parse_setting as nlm_settings
 from . import degrade
 from .degrade import Degradations, degrade_jpeg, degrade_blur, degrade_pointwise, gaussian_taps
 from . import neighbor
@@ -94,7 +97,8 @@ if pretrained_dir.is_dir():
         }
 
 
-def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None, pixel_shuffle=None, burst=None):
+def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None, pixel_shuffle=None, burst=None,
+               nlm=None):
     """bfcnn/__init__.py:81-97: a registry name, a model directory (pipeline.json + weights.npz written by
     `save_model`), or a `.keras` archive of a trained unet_laplacian hydra / the directory holding `model_hydra.keras`
     (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]: a
@@ -109,7 +113,12 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
     StabilisedDenoiserModule for camera noise whose variance is gain x + offset: True fits the pair per frame, a pair fixes it
     (vst.py).  `burst` = True or a dict of BurstDenoiserModule's settings (reference, levels, search, sigma, k) wraps the result,
     outermost, in a BurstDenoiserModule: the callable then takes uint8 [B,T,H,W,C] bursts, aligns and merges their frames and
-    denoises the merged frame (burst.py)."""
+    denoises the merged frame (burst.py).  The name "nlm" is no network: it returns a NlmDenoiserModule (non-local means, nlm.py;
+    any channel count 1..4, no weights) under the same wrappers; `nlm` = None or a dict of its settings (sigma, patch, search,
+    strength), a ValueError with any other `model_path`."""
+    if nlm is not None and model_path != _nlm.MODEL_NAME:
+        raise ValueError(f"nlm sets the non-local means of load_model({_nlm.MODEL_NAME!r}), got it with model_path {model_path!r}")
+    filter_settings = nlm_settings(nlm) if model_path == _nlm.MODEL_NAME else None     # refused before anything is loaded
     if stabilise is not None and not isinstance(stabilise, (bool, tuple, list)):
         raise ValueError(f"stabilise must be None, a bool or a (gain, offset) pair, got {stabilise!r}")
     if stabilise is not None and not isinstance(stabilise, bool):
@@ -120,7 +129,7 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
         raise ValueError(f"tiled may set tile, overlap, margin and tile_batch, got {sorted(tiled)}")
     shuffle = pixel_shuffle_settings(pixel_shuffle)              # a bad setting is refused before anything is loaded
     merge = burst_settings(burst)
-    module = _load_module(model_path, device)
+    module = _load_module(model_path, device) if filter_settings is None else NlmDenoiserModule(**filter_settings)
     if self_ensemble is not None:
         module = SelfEnsembleDenoiserModule(module, transforms=self_ensemble)
     if tiled is not None and tiled is not False:

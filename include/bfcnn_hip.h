@@ -781,6 +781,24 @@ int bf_burst_align(const uint8_t* frames, int B, int T, int H, int W, int C, int
 int bf_op_burst_merge(const uint8_t* frames, const int* field, const int64_t* thresholds, int B, int T, int H, int W, int C, int ref,
                       void* out, int out_is_u8, int* counts_or_null, void* stream);
 
+/* ---- non-local means: a denoiser without weights (Buades, Coll, Morel 2005; blind_image_denoising_amd/nlm.py is the host side;
+ * csrc/nlm.hip) ----
+ * images = uint8 [B,H,W,C], C in 1..4, B H W C < 2^31; `patch` = p in 1..3, `search` = r in 1..10; n = C (2 p + 1)^2.
+ * table = int32 [1024], TABLE[i] = rint(4096 exp(-(i + 0.5) 9 / 1024)) for i < 1023, TABLE[1023] = 0 (nlm.nlm_table builds it; the
+ * kernel evaluates no exponential).  params = int64 [B,2] = (offset, mult) per image, 0 <= offset, 0 <= mult <= 2^32 - 1 (values
+ * outside are clamped to that range; nlm.nlm_params makes them from a noise level).  P = the image with edge replication.
+ * Pixel x, every offset d != 0 with |dy|, |dx| <= r and q = x + d inside the frame (candidates outside are left out):
+ *   D = sum over c and |u|, |v| <= p of (P[x + (u,v), c] - P[q + (u,v), c])^2  (< 2^24);  a = max(D - offset, 0);
+ *   idx = min((a mult) >> 32, 1023) (a 64-bit product);  w = TABLE[idx] -- but every w is 0 when mult == 2^32 - 1: the filter is
+ *   off, the image comes back unchanged;
+ *   the centre gets w_c = max(1, max_q w);  num_c = sum_q w I[q,c] + w_c I[x,c],  den = sum_q w + w_c  (both < 2^31);
+ *   out [B,H,W,C] = (float) ((double) num_c / (double) den): one correctly rounded division, one cast (cast_to_uint8 == 0), or
+ *   uint8 (2 num_c + den) / (2 den) (integer division).  weights_or_null = int32 [B,H,W] = den.
+ * Sums of integers: the result does not depend on the launch geometry.  One launch, no allocation, no synchronisation:
+ * graph-capturable.  BF_EINVAL for NULL, a bad shape or setting, a misaligned pointer, or out == images. */
+int bf_op_nlm(const uint8_t* images, const int64_t* params, const int32_t* table, int B, int H, int W, int C, int patch, int search,
+              void* out, int cast_to_uint8, int32_t* weights_or_null, void* stream);
+
 /* ---- risk estimation without a clean image: Stein's unbiased risk estimate around a denoiser (blind_image_denoising_amd/risk.py
  * is the host side; csrc/risk.hip).  For y = x + n, n ~ N(0, sigma^2): E |f(y) - x|^2 / N = E[ |f(y) - y|^2 / N - sigma^2 +
  * (2 sigma^2 / N) div f(y) ], div f(y) ~ s . (f(y + a s) - f(y)) / a for a random sign vector s (Ramani, Blu, Unser 2008).

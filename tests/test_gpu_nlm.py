@@ -1,0 +1,219 @@
+"""GPU tests of csrc/nlm.hip and NlmDenoiserModule.
+
+Yardstick: tests/nlm_reference.py.  The kernel adds, multiplies, compares and shifts integers, reads a table that NumPy built,
+and makes one correctly rounded fp64 division and one cast, each of which NumPy does bit for bit the same: every comparison of a
+filtered image here is exact (dtype, shape, array_equal)."""
+import numpy as np
+import pytest
+import torch
+
+import blind_image_denoising_amd as bf
+import burst_reference
+import nlm_reference as R
+import risk_reference
+import tiling_reference
+
+pytestmark = pytest.mark.gpu
+
+# (H, W, C, patch, search) at B = 2.  3 x 5 is smaller than a patch and than the search window, 16 x 16 lies inside one 32 x 32
+# tile, 37 x 45 is odd with cut edge tiles, 70 x 83 has three tiles each way, so that a search window of 10 crosses tile borders
+CASES = [(3, 5, 1, 1, 1), (3, 5, 3, 3, 10), (3, 5, 4, 2, 3),
+         (16, 16, 3, 1, 10), (16, 16, 1, 2, 3), (16, 16, 4, 3, 1),
+         (37, 45, 3, 1, 10), (37, 45, 1, 3, 3), (37, 45, 4, 2, 10), (37, 45, 3, 2, 1),
+         (70, 83, 3, 1, 10), (70, 83, 1, 2, 10), (70, 83, 4, 3, 3), (70, 83, 3, 3, 10)]
+_ids = {"ids": lambda c: "-".join(map(str, c))}
+SIGMAS, STRENGTHS = [9.0, 14.0], np.array([0.55, 0.75])             # different parameters per image, around the scenes' sigma of 12
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _same(got, ref):
+    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
+    return got.dtype == ref.dtype and got.shape == ref.shape and np.array_equal(got, ref)
+
+
+def _scene(H, W, C, seed, sigma=12.0, B=2):
+    """structure plus noise: 4 x 4 blocks over smooth blobs, a flat quarter (patches that repeat) and two single bright pixels
+    (patches that nothing resembles), under white noise of `sigma`"""
+    rng = np.random.default_rng(seed)
+    images = np.empty((B, H, W, C), np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    for b in range(B):
+        blocks = np.kron(rng.integers(0, 120, (-(H // -4), -(W // -4), C)), np.ones((4, 4, 1), np.int64))[:H, :W]
+        blobs = 60 + 60 * np.sin(yy / 7.0 + seed + b)[..., None] * np.cos(xx / 5.0)[..., None]
+        clean = np.clip(blocks + blobs, 0, 255).astype(np.float64)
+        clean[:H // 2, :W // 2] = 40.0
+        noisy = np.clip(np.rint(clean + rng.normal(0.0, sigma, clean.shape)), 0, 255)
+        if H >= 16:
+            noisy[H // 4, W // 4] = 255
+            noisy[H - 3, W - 4] = 255
+        images[b] = noisy
+    return images
+
+
+@pytest.mark.parametrize("case", CASES, **_ids)
+def test_every_output_form_matches_numpy(case):
+    H, W, C, p, r = case
+    images = _scene(H, W, C, seed=sum(case))
+    prm = R.params(SIGMAS, C, p, STRENGTHS)
+    num, den, wmax, zeros = R.nlm_many(images, [prm], p, r)[0]
+    want_u8, want_f32, want_w = R.finish(num, den, True), R.finish(num, den, False), den.astype(np.int32)
+    d_images, d_prm = _dev(images), _dev(prm)
+    got_u8, got_w = bf.nlm(d_images, d_prm, p, r, return_weights=True)
+    assert got_u8.is_cuda and _same(got_u8, want_u8) and _same(got_w, want_w), "uint8 with weights"
+    got_f32 = bf.nlm(d_images, d_prm, p, r, cast_to_uint8=False)
+    assert isinstance(got_f32, torch.Tensor) and _same(got_f32, want_f32), "float32 without weights"
+    assert _same(bf.nlm(d_images, d_prm, p, r), want_u8), "uint8 without weights"
+    assert _same(bf.nlm(d_images, d_prm, p, r, False, True)[1], want_w), "float32 with weights"
+    if (p, r) == (1, 10) and H >= 37:                                # the scenes reach the three weight branches
+        assert (den == 1).any() and (zeros > 0).any() and (wmax == R.table()[0]).any()
+        assert ((den > 1) & (wmax < R.table()[0])).any()
+    for b in range(2):                                               # an image inside a batch gets the bits of that image alone
+        assert _same(bf.nlm(d_images[b:b + 1], d_prm[b:b + 1], p, r, False), want_f32[b:b + 1])
+
+
+def test_the_clamp_switches_the_filter_off_for_one_image_of_a_batch():
+    images = _scene(37, 45, 3, seed=3)
+    prm = R.params([0.0, 12.0], 3, 2, 0.55)
+    assert prm[0].tolist() == [0, R.MULT_OFF]
+    for cast in (True, False):
+        out, weights = bf.nlm(_dev(images), _dev(prm), 2, 5, cast, True)
+        want, want_w = R.nlm(images, prm, 2, 5, cast)
+        assert _same(out, want) and _same(weights, want_w)
+        out = out.cpu().numpy()
+        assert np.array_equal(out[0], images[0]) and (weights[0] == 1).all().item()
+        assert (out[1] != images[1]).mean() > 0.5 and (weights[1] > 4096).any().item()
+
+
+def test_params_on_the_device_are_numpy():
+    sigmas = np.array([0.0, 0.5, 1.0, 7.25, 10.83, 20.0, 63.999, 255.0])
+    strengths = np.array([0.25, 0.4, 0.55, 0.75, 1.0, 1.4, 4.0, 0.0])
+    for C, p in ((1, 1), (3, 1), (3, 2), (4, 3)):
+        for strength in (0.55, 4.0, strengths, _dev(strengths)):
+            got = bf.nlm_params(_dev(sigmas), C, p, strength)
+            ref = R.params(sigmas, C, p, strength.cpu().numpy() if isinstance(strength, torch.Tensor) else strength)
+            assert got.is_cuda and _same(got, ref)
+
+
+# ---- the module --------------------------------------------------------------------------------------------------------------
+
+def test_module_is_the_reference():
+    images = _scene(37, 45, 3, seed=11)
+    prm = R.params(SIGMAS, 3, 2, 0.75)
+    want, want_w = R.nlm(images, prm, 2, 5)
+    module = bf.NlmDenoiserModule(sigma=SIGMAS, patch=2, search=5, strength=0.75)
+    got = module(images)                                             # NumPy in, NumPy out
+    assert isinstance(got, np.ndarray) and _same(got, want) and _same(module.last_weights, want_w)
+    got = module(_dev(images))                                       # device tensor in, device tensor out
+    assert isinstance(got, torch.Tensor) and got.is_cuda and _same(got, want)
+    flt = module.float_form()
+    assert _same(flt(_dev(images)), R.nlm(images, prm, 2, 5, False)[0])
+    assert flt.last_weights is module.last_weights and _same(flt.last_weights, want_w)
+    per_channel = np.array([[9.0, 9.0, 9.0], [14.0, 14.0, 14.0]])    # [B,C]: the root mean square over the channels
+    assert _same(bf.NlmDenoiserModule(sigma=per_channel, patch=2, search=5, strength=0.75)(images), want)
+    grey = images[..., :1]                                           # one channel; strength per image
+    module = bf.NlmDenoiserModule(sigma=_dev(np.array(SIGMAS)), search=3, strength=STRENGTHS)
+    assert _same(module(grey), R.nlm(grey, R.params(SIGMAS, 1, 1, STRENGTHS), 1, 3)[0])
+    assert module(images[:0]).shape == (0, 37, 45, 3)
+
+
+def test_module_estimates_sigma_on_the_device():
+    images = _scene(37, 45, 3, seed=12)
+    sigma = bf.estimate_noise(_dev(images), "mad")
+    got = bf.NlmDenoiserModule(search=5)(_dev(images))
+    assert torch.equal(got, bf.nlm(_dev(images), bf.nlm_params(sigma, 3, 1, 0.55), 1, 5))
+    assert _same(got, R.nlm(images, R.params(sigma.cpu().numpy(), 3, 1, 0.55), 1, 5)[0])
+
+
+def test_inside_the_tiling_wrapper_it_is_the_hand_built_pipeline():
+    images = _scene(37, 45, 3, seed=13)
+    T, O, M = 16, 8, 2
+    module = bf.TiledDenoiserModule(bf.NlmDenoiserModule(sigma=10.0, search=3), tile=T, overlap=O, margin=M, tile_batch=5)
+    tiles = tiling_reference.split(images, T, O)
+    filtered = R.nlm(tiles, R.params(np.full(len(tiles), 10.0), 3, 1, 0.55), 1, 3, False)[0]
+    want = tiling_reference.blend(filtered, 2, 37, 45, T, O, M, True)
+    assert _same(module(images), want) and module.last_plan.tiles > 1 and module.check_status() is True
+    assert _same(module(_dev(images)), want)
+
+
+def test_inside_the_burst_wrapper_it_is_the_hand_built_pipeline():
+    rng = np.random.default_rng(14)
+    base = _scene(37 + 8, 45 + 8, 3, seed=14, sigma=0.0, B=1)[0].astype(np.float64)
+    frames = np.empty((2, 3, 37, 45, 3), np.uint8)
+    for b in range(2):
+        for t in range(3):
+            dy, dx = rng.integers(0, 9, 2)
+            frames[b, t] = np.clip(np.rint(base[dy:dy + 37, dx:dx + 45] + rng.normal(0.0, 6.0, (37, 45, 3))), 0, 255)
+    module = bf.BurstDenoiserModule(bf.NlmDenoiserModule(sigma=4.0, search=3), levels=2, search=3, sigma=6.0)
+    field = burst_reference.align(frames, 0, 2, 3)
+    merged, counts = burst_reference.merge(frames, field, burst_reference.thresholds([6.0, 6.0], 3), 0)
+    filtered = R.nlm(merged, R.params([4.0, 4.0], 3, 1, 0.55), 1, 3, False)[0]
+    want = np.rint(np.clip(filtered, 0.0, 255.0)).astype(np.uint8)
+    assert _same(module(frames), want) and _same(module.last_counts, counts)
+    assert _same(module.float_form()(_dev(frames)), filtered)
+
+
+def test_a_call_with_a_fixed_sigma_replays_from_a_graph():
+    module = bf.NlmDenoiserModule(sigma=12.0, search=5)
+    a, b = _dev(_scene(37, 45, 3, seed=15)), _dev(_scene(37, 45, 3, seed=16))
+    want_a, want_b = module(a), module(b)                            # direct calls (also the upload of the table)
+    static_in = a.clone()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        static_out = module(static_in)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(static_out, want_a)
+    static_in.copy_(b)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(static_out, want_b) and not torch.equal(want_a, want_b)
+
+
+# ---- quality and tuning ------------------------------------------------------------------------------------------------------
+
+_LENA = []
+
+
+def _lena():
+    if not _LENA:
+        _LENA.append(R.load_lena())
+    return _LENA[0]
+
+
+def test_load_model_nlm_gains_six_decibels_on_lena():
+    clean, noisy = R.noisy_crop(_lena(), slice(128, 384), slice(128, 384), 20.0)
+    module = bf.load_model("nlm")
+    assert type(module) is bf.NlmDenoiserModule
+    out = module(noisy)
+    gain = R.psnr(out, clean) - R.psnr(noisy, clean)
+    print(f"noisy {R.psnr(noisy, clean):.2f} dB, nlm {R.psnr(out, clean):.2f} dB")
+    assert out.dtype == np.uint8 and out.shape == noisy.shape and gain >= 6.0, gain
+    grey = noisy[..., 1:2]                                           # grey-scale frames: nothing else in the package takes them
+    assert R.psnr(bf.load_model("nlm", nlm={"search": 7})(grey), clean[..., 1:2]) - R.psnr(grey, clean[..., 1:2]) >= 5.0
+
+
+def test_tuning_picks_the_strength_the_reference_picks():
+    """tests/test_nlm.py shows with the reference that SURE and the true error both pick 0.75 on this crop; the filter here is the
+    reference bit for bit (above), so the choice is the one computed there"""
+    clean, noisy = R.noisy_crop(_lena(), slice(192, 320), slice(192, 320), 10.0)
+    best, mse = bf.nlm_tune(_dev(noisy), sigma=10.0, probes=2, amplitude=1, seed=5)
+    assert best.is_cuda and best.dtype == mse.dtype == torch.float64 and best.tolist() == [0.75] and mse.shape == (1, 6)
+    # the estimate itself: the reference's SURE arithmetic around this filter.  The two sums of 49 152 fp64 terms differ in their
+    # order alone (<= 49 152 eps = 1.1e-11 relative each); the MSE is their combination minus sigma^2, of the terms' own size
+    for k, strength in enumerate(R.STRENGTHS):
+        prm = _dev(np.tile(R.params([10.0], 3, 1, strength), (3, 1)))
+        want = risk_reference.estimate_risk(lambda stack: bf.nlm(_dev(stack), prm, cast_to_uint8=False).cpu().numpy(), noisy, 10.0,
+                                            probes=2, amplitude=1, seed=5)["mse"][0]
+        assert abs(mse[0, k].item() - want) <= 1e-8 * 100.0, (strength, mse[0, k].item(), want)
+    true_mse = [np.mean((bf.nlm(noisy, _dev(R.params([10.0], 3, 1, s)), cast_to_uint8=False).astype(np.float64) - clean) ** 2)
+                for s in R.STRENGTHS]
+    assert R.STRENGTHS[int(np.argmin(true_mse))] == 0.75
+    best_np, mse_np = bf.nlm_tune(noisy, sigma=10.0, seed=5)         # NumPy in, NumPy out
+    assert isinstance(best_np, np.ndarray) and np.array_equal(best_np, best.cpu().numpy()) and np.array_equal(mse_np, mse.cpu().numpy())
+    auto = bf.NlmDenoiserModule(sigma=10.0, strength="auto")         # tunes per call (seed 0)
+    chosen = bf.nlm_tune(_dev(noisy), sigma=10.0)[0]
+    assert torch.equal(auto(_dev(noisy)), bf.nlm(_dev(noisy), bf.nlm_params(_dev(np.array([10.0])), 3, 1, chosen)))

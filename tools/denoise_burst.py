@@ -64,7 +64,7 @@ def main(argv=None):
     if not args.merge_only:
         tiled = None if args.tile is None else {"tile": args.tile, "tile_batch": args.tile_batch}
         inner = bf.load_model(args.model, tiled=tiled)
-        channels = int(inner.model_hydra.desc.in_channels)
+        channels = 3 if inner.model_hydra is None else int(inner.model_hydra.desc.in_channels)      # "nlm" has no model: colour
     os.makedirs(args.out_dir, exist_ok=True)
     written = []
     for name, files in bursts.items():

@@ -4,7 +4,8 @@ table, measured on the GPU by blind_image_denoising_amd.evaluate.  It reads only
 
     python tools/evaluate.py unet_laplacian_v5.6 frames/*.png --noise-std 10 15 20 25 30 --json report.json
 
-MODEL is a registry name (blind_image_denoising_amd.models) or a model directory; IMAGES are files or directories.  Every image is
+MODEL is a registry name (blind_image_denoising_amd.models), a model directory or `nlm` (non-local means: the classical baseline
+to put next to a network's numbers); IMAGES are files or directories.  Every image is
 its own batch, so frames of different sizes can be mixed; --size H W resizes them first."""
 import argparse
 import json
@@ -35,7 +36,7 @@ def main(argv=None):
         files += sorted(image_filenames_generator(directory=[p], verbose=False)()) if os.path.isdir(p) else [p]
     if not files:
         ap.error("no image files")
-    channels = int(module.model_hydra.desc.in_channels)
+    channels = 3 if module.model_hydra is None else int(module.model_hydra.desc.in_channels)      # "nlm" has no model: colour
     size = None if args.size is None else tuple(args.size)
     batches = [np.asarray(bf.load_image(path=f, image_size=size, num_channels=channels, expand_dims=True, normalize=False), np.uint8)
                for f in files]

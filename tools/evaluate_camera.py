@@ -36,7 +36,7 @@ def main(argv=None):
                     help="write the report as strict JSON to this file; without a file name, print it instead of the table")
     args = ap.parse_args(argv)
     module = bf.load_model(args.model, self_ensemble=args.self_ensemble)
-    channels = int(module.model_hydra.desc.in_channels)
+    channels = 3 if module.model_hydra is None else int(module.model_hydra.desc.in_channels)      # "nlm" has no model: colour
     files = sorted(image_filenames_generator(directory=[args.dir], verbose=False)()) if os.path.isdir(args.dir) else [args.dir]
     if not files:
         ap.error("no image files")

@@ -39,7 +39,7 @@ def main(argv=None):
                     help="write the report as strict JSON to this file; without a file name, print it instead of the table")
     args = ap.parse_args(argv)
     module = bf.load_model(args.model, self_ensemble=args.self_ensemble)
-    channels = int(module.model_hydra.desc.in_channels)
+    channels = 3 if module.model_hydra is None else int(module.model_hydra.desc.in_channels)      # "nlm" has no model: colour
     files = []
     for p in args.images:
         files += sorted(image_filenames_generator(directory=[p], verbose=False)()) if os.path.isdir(p) else [p]
