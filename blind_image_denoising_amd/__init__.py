@@ -52,6 +52,9 @@ from .burst import parse_setting as burst_settings
 from . import nlm as _nlm
 from .nlm import NlmDenoiserModule, nlm, nlm_params, nlm_table, nlm_tune
 from .nlm import parse_setting as nlm_settings
+from . import restore as _restore
+from .restore import (RestoreConstraint, RestoreResult, mask_constraint, block_constraint, restore_init, restore_direction,
+                      restore_step, restore_finish, restore, inpaint, super_resolve, bayer_mask)
 from . import degrade
 from .degrade import Degradations, degrade_jpeg, degrade_blur, degrade_pointwise, gaussian_taps
 from . import neighbor

@@ -196,6 +196,11 @@ SIGNATURES = {
     "bf_burst_align": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I64, _P, _P]),
     "bf_op_burst_merge": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "bf_op_nlm": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "bf_op_restore_scratch_bytes": (_I64, [_I, _I, _I, _I]),
+    "bf_op_restore_init": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _D, C.c_uint64, _P, _P]),
+    "bf_op_restore_direction": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I64, _P, _P]),
+    "bf_op_restore_step": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _D, _D, _I, C.c_uint64, _P, _P, _I, _P, _P]),
+    "bf_op_restore_finish": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _I, _P]),
     "bf_op_risk_probe_u8": (_I,[_P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _P]),
     "bf_op_risk_sums_scratch_bytes": (_I64, [_I, _I, _I, _I, _I]),
     "bf_op_risk_sums": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_uint64, _P, _I64, _P, _P]),

@@ -32,7 +32,7 @@ constexpr int PS_BINS_PAD = BF_MEDIAN_BINS_PAD;                  // q is an inte
 constexpr int PS_ROW_BYTES = (PS_PX + PS_MAXS) * PS_MAXC;        // LDS row pitch of the staged tile
 constexpr int PS_THREADS = 256;
 constexpr unsigned PS_PHILOX_STREAM = 5u;                        // counter word 3; 0 and 1: augment.hip, 2: risk.hip, 3: camera noise and
-                                                                 // neighbor.hip, 4: degrade.hip
+                                                                 // neighbor.hip, 4: degrade.hip, 6: restore.hip
 
 struct PsTiles {
     int x, y;

@@ -799,6 +799,50 @@ int bf_op_burst_merge(const uint8_t* frames, const int* field, const int64_t* th
 int bf_op_nlm(const uint8_t* images, const int64_t* params, const int32_t* table, int B, int H, int W, int C, int patch, int search,
               void* out, int cast_to_uint8, int32_t* weights_or_null, void* stream);
 
+/* ---- restoration with the denoiser's implicit prior: the state update of Kadkhodaie & Simoncelli, "Stochastic solutions for linear
+ * inverse problems using the prior implicit in a denoiser" (NeurIPS 2021), Algorithm 2, between two denoiser calls
+ * (blind_image_denoising_amd/restore.py is the host side; csrc/restore.hip) ----
+ * Images are float32 [B,H,W,C] on the 0..255 scale, C in 1..4, n = H W C < 2^31.  A constraint is an orthogonal projection P and an
+ * anchor a = the measurement embedded in image space:
+ *   kind 0 (mask):  mask = uint8 [B,H,W,mask_channels], mask_channels = 1 (all channels) or C; m = (mask != 0); P v = m v;
+ *                   anchor = the measured image [B,H,W,C], uint8 or float32 (anchor_is_u8); its values where m = 0 are never read.
+ *   kind 1 (block): factor = s in 2..8, H and W multiples of s; P v = every s x s block of every channel replaced by its mean;
+ *                   anchor = the low-resolution image [B,H/s,W/s,C], uint8 or float32; a = it repeated s x s.  mask is not read.
+ * Every output element is formed in fp64 from its float32 operands and rounded to float32 once.
+ * z_t = standard normals: elements 4 g .. 4 g + 3 of an image (flat index inside the image) share philox4x32_10(counter = (g,
+ *   sample_id, t, 6), key = (lo32 seed, hi32 seed)); words (0, 1) give elements 4 g and 4 g + 1 as the cosine and sine branch of
+ *   Box-Muller with u1 = ((r0 >> 8) + 1) / 2^24, u2 = (r1 >> 8) / 2^24, words (2, 3) elements 4 g + 2 and 4 g + 3 in the same way.
+ *   sample_id = uint32 [B] on the device, NULL: the image's index b.
+ * No entry uploads, allocates or synchronises: graph-capturable.  BF_EINVAL for NULL, C outside 1..4, n >= 2^31, s outside 2..8, H
+ * or W no multiple of s, mask_channels neither 1 nor C, a misaligned pointer, aliased outputs, short scratch; nothing is launched.
+ *
+ * bf_op_restore_init:      y = 127.5 (1 - P 1) + a + sigma_0 z_0   (mask: a where measured, 127.5 elsewhere; block: a).
+ * bf_op_restore_direction: d = D - y + a - P D  (= (I - P)(D - y) + (a - P y); the mask form selects a - y or D - y) from y and
+ *   D = `denoised`; sumsq = double [B] = sum over the image of d^2, of the fp64 values before their rounding to float32.  The sum
+ *   is the fixed-order two-stage sum of csrc/block_reduce.h through `scratch` (bf_op_restore_scratch_bytes bytes, 8-byte aligned;
+ *   no atomics): the same bits in two calls, and for an image alone or inside a batch.  d must not alias y or denoised.
+ * bf_op_restore_step:      iteration t >= 1 with the step size h_t in (0, 1], beta in [0, 1], sigma_l > 0.  Per image, all on the
+ *   device: sigma_t = sqrt(sumsq / n); trace_or_null = double [trace_rows, B] gets trace[t - 1][b] = sigma_t (t <= trace_rows);
+ *   the image MOVES when steps[b] == t - 1 (it has moved in every iteration before) and sigma_t > sigma_l:
+ *   gamma_t^2 = ((1 - beta h_t)^2 - (1 - h_t)^2) sigma_t^2,  y += h_t d + gamma_t z_t  in place,  steps[b] = t;
+ *   else it is frozen: y and steps[b] (int32 [B], zero before t = 1) stay as they are, now and in every later iteration.
+ *   No noise is drawn when gamma_t = 0 (beta = 1).  y must not alias d.
+ * bf_op_restore_finish:    x = D - P D + a from D = the denoiser's output for the final y; with a mask the measured samples are
+ *   the measurement itself (a select, not arithmetic).  out = float32 [B,H,W,C], or uint8 (out_is_u8): rounded half to even and
+ *   clipped to 0..255, as the head kernel does.  out must not alias denoised. */
+int64_t bf_op_restore_scratch_bytes(int B, int H, int W, int C);
+int bf_op_restore_init(float* y, int B, int H, int W, int C, int kind, const uint8_t* mask, int mask_channels, int factor,
+                       const void* anchor, int anchor_is_u8, double sigma_0, uint64_t seed, const uint32_t* sample_id_or_null,
+                       void* stream);
+int bf_op_restore_direction(const float* y, const float* denoised, int B, int H, int W, int C, int kind, const uint8_t* mask,
+                            int mask_channels, int factor, const void* anchor, int anchor_is_u8, float* d, void* scratch,
+                            int64_t scratch_bytes, double* sumsq, void* stream);
+int bf_op_restore_step(float* y, const float* d, const double* sumsq, int B, int H, int W, int C, double h_t, double beta,
+                       double sigma_l, int t, uint64_t seed, const uint32_t* sample_id_or_null, double* trace_or_null, int trace_rows,
+                       int* steps, void* stream);
+int bf_op_restore_finish(const float* denoised, int B, int H, int W, int C, int kind, const uint8_t* mask, int mask_channels,
+                         int factor, const void* anchor, int anchor_is_u8, void* out, int out_is_u8, void* stream);
+
 /* ---- risk estimation without a clean image: Stein's unbiased risk estimate around a denoiser (blind_image_denoising_amd/risk.py
  * is the host side; csrc/risk.hip).  For y = x + n, n ~ N(0, sigma^2): E |f(y) - x|^2 / N = E[ |f(y) - y|^2 / N - sigma^2 +
  * (2 sigma^2 / N) div f(y) ], div f(y) ~ s . (f(y + a s) - f(y)) / a for a random sign vector s (Ramani, Blu, Unser 2008).
