@@ -49,6 +49,9 @@ from .pixel_shuffle import parse_setting as pixel_shuffle_settings
 from . import burst
 from .burst import BurstDenoiserModule, burst_pyramid, burst_align, burst_thresholds, burst_merge
 from .burst import parse_setting as burst_settings
+from . import video as _video
+from .video import VideoDenoiserModule, VideoState, video_state, video_update
+from .video import parse_setting as video_settings
 from . import nlm as _nlm
 from .nlm import NlmDenoiserModule, nlm, nlm_params, nlm_table, nlm_tune
 from .nlm import parse_setting as nlm_settings
@@ -101,7 +104,7 @@ if pretrained_dir.is_dir():
 
 
 def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None, pixel_shuffle=None, burst=None,
-               nlm=None):
+               nlm=None, video=None):
     """bfcnn/__init__.py:81-97: a registry name, a model directory (pipeline.json + weights.npz written by
     `save_model`), or a `.keras` archive of a trained unet_laplacian hydra / the directory holding `model_hydra.keras`
     (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]: a
@@ -116,7 +119,10 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
     StabilisedDenoiserModule for camera noise whose variance is gain x + offset: True fits the pair per frame, a pair fixes it
     (vst.py).  `burst` = True or a dict of BurstDenoiserModule's settings (reference, levels, search, sigma, k) wraps the result,
     outermost, in a BurstDenoiserModule: the callable then takes uint8 [B,T,H,W,C] bursts, aligns and merges their frames and
-    denoises the merged frame (burst.py).  The name "nlm" is no network: it returns a NlmDenoiserModule (non-local means, nlm.py;
+    denoises the merged frame (burst.py).  `video` = True or a dict of VideoDenoiserModule's settings (n_max, levels, search, sigma,
+    k) wraps the result, outermost, in a VideoDenoiserModule instead: the callable then takes the next uint8 [B,H,W,C] frame of B
+    parallel streams, filters it recursively along the motion and denoises the filtered frame (video.py); together with `burst` a
+    ValueError.  The name "nlm" is no network: it returns a NlmDenoiserModule (non-local means, nlm.py;
     any channel count 1..4, no weights) under the same wrappers; `nlm` = None or a dict of its settings (sigma, patch, search,
     strength), a ValueError with any other `model_path`."""
     if nlm is not None and model_path != _nlm.MODEL_NAME:
@@ -132,6 +138,9 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
         raise ValueError(f"tiled may set tile, overlap, margin and tile_batch, got {sorted(tiled)}")
     shuffle = pixel_shuffle_settings(pixel_shuffle)              # a bad setting is refused before anything is loaded
     merge = burst_settings(burst)
+    stream = video_settings(video)
+    if merge is not None and stream is not None:
+        raise ValueError("burst and video both wrap outermost: set one of them")
     module = _load_module(model_path, device) if filter_settings is None else NlmDenoiserModule(**filter_settings)
     if self_ensemble is not None:
         module = SelfEnsembleDenoiserModule(module, transforms=self_ensemble)
@@ -141,6 +150,8 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
         module = PixelShuffleDenoiserModule(module, **shuffle)
     if stabilise is not None and stabilise is not False:
         module = StabilisedDenoiserModule(module, None if stabilise is True else stabilise)
+    if stream is not None:
+        return VideoDenoiserModule(module, **stream)
     return module if merge is None else BurstDenoiserModule(module, **merge)
 
 

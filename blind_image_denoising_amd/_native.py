@@ -195,6 +195,7 @@ SIGNATURES = {
     "bf_burst_align_scratch_bytes": (_I64, [_I, _I, _I, _I, _I, _I]),
     "bf_burst_align": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I64, _P, _P]),
     "bf_op_burst_merge": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "bf_op_video_update": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "bf_op_nlm": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "bf_op_restore_scratch_bytes": (_I64, [_I, _I, _I, _I]),
     "bf_op_restore_init": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _D, C.c_uint64, _P, _P]),

@@ -781,6 +781,30 @@ int bf_burst_align(const uint8_t* frames, int B, int T, int H, int W, int C, int
 int bf_op_burst_merge(const uint8_t* frames, const int* field, const int64_t* thresholds, int B, int T, int H, int W, int C, int ref,
                       void* out, int out_is_u8, int* counts_or_null, void* stream);
 
+/* ---- video: one step of the recursive motion-compensated temporal filter (blind_image_denoising_amd/video.py is the host side;
+ * csrc/video.hip) ----
+ * The state of B parallel streams: acc = uint16 [B,H,W,C], the accumulated frame times 256, in 0..65280; cnt = uint16 [B,H,W], the
+ * number of frames in a pixel times 256, 0 = empty.  The state's image is state8 = (acc + 128) >> 8 as uint8.
+ * x = uint8 [B,H,W,C] the new frame, C in 1..4; field = int32 [B,gy,gx,2] as (dy, dx) on the 16 x 16 tiles of bf_burst_align (its
+ * field of frame 1 of the pair (x, state8_in) with ref 0), any int32 (clamp saturates); thresholds = int64 [B,2] = (lo, hi) per
+ * image, 0 <= lo < hi < 2^54; n_max in 1..64 the temporal support.  clamp(p) clips a coordinate to the frame.  All integers, for
+ * pixel p in tile (p_y / 16, p_x / 16) with displacement d:
+ *   D = sum over q in the 5 x 5 window around p (q clamped first), over the channels, of (state8_in(clamp(q + d)) - x(q))^2;
+ *   w = 256 if D <= lo, 0 if D >= hi, else ((hi - D) 256) / (hi - lo)   (the ramp of bf_op_burst_merge);
+ *   s = clamp(p + d);  n = min(cnt_in(s), 256 (n_max - 1));  m = (w n) >> 8;  den = 256 + m;
+ *   acc_out(p, c) = (65536 x(p, c) + m acc_in(s, c) + (den >> 1)) / den;  cnt_out(p) = den;
+ *   image_out(p, c) = uint8 (acc_out + 128) >> 8, the image of the new state (what the next step aligns against, and the uint8
+ *   output);  out_f32_or_null(p, c) = float32 acc_out / 256 (exact).
+ * An empty state passes the frame through (acc = 256 x, cnt = 256) whatever field and acc_in hold; so does n_max = 1.
+ * state8_in is derived from acc_in, not read.  Scalars only: no upload, no allocation, no synchronisation, graph-capturable.
+ * BF_EINVAL for NULL (but out_f32_or_null), a bad shape or setting, n_max outside 1..64, misaligned pointers (2 bytes for acc and
+ * cnt, 4 for field and out_f32, 8 for thresholds), frames beyond the kernel's 32-bit arithmetic (H W C > 2^29 - 1,
+ * B (H W / 16 + H + W + 1) > 2^29 - 1), and when an output overlaps an input or another output: a tile reads its neighbours'
+ * frame and state, the step is not in place. */
+int bf_op_video_update(const uint8_t* x, const uint16_t* acc_in, const uint16_t* cnt_in, const int* field, const int64_t* thresholds,
+                       int B, int H, int W, int C, int n_max, uint16_t* acc_out, uint16_t* cnt_out, uint8_t* image_out,
+                       float* out_f32_or_null, void* stream);
+
 /* ---- non-local means: a denoiser without weights (Buades, Coll, Morel 2005; blind_image_denoising_amd/nlm.py is the host side;
  * csrc/nlm.hip) ----
  * images = uint8 [B,H,W,C], C in 1..4, B H W C < 2^31; `patch` = p in 1..3, `search` = r in 1..10; n = C (2 p + 1)^2.
