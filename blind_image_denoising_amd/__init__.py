@@ -18,7 +18,8 @@ from .custom_logger import logger
 from .utilities import load_config, save_config, input_shape_fixer
 from .model import (BuilderResults, HydraModel, model_builder, describe_resnet, save_model, load_hydra,
                     build_normalize_model, build_denormalize_model)
-from .module_denoiser import DenoiserModule, GraphedDenoiserModule
+from .module_denoiser import DenoiserModule, DenoiserWrapper, GraphedDenoiserModule
+from . import self_ensemble as _self_ensemble
 from .self_ensemble import SelfEnsembleDenoiserModule
 from .loss import loss_function_builder
 from .optimizer import optimizer_builder, schedule_builder, deep_supervision_schedule_builder
@@ -103,56 +104,52 @@ if pretrained_dir.is_dir():
         }
 
 
+# load_model's wrappers, innermost first: (keyword, its parse_setting: the option's value -> the keyword arguments of the wrapper,
+# or None for no wrapper, ValueError for a bad one; the wrapper).  burst and video both go outermost: one of them at most
+_WRAPPERS = (("self_ensemble", _self_ensemble.parse_setting, SelfEnsembleDenoiserModule),
+             ("tiled", tiling.parse_setting, TiledDenoiserModule),
+             ("pixel_shuffle", pixel_shuffle_settings, PixelShuffleDenoiserModule),
+             ("stabilise", vst.parse_setting, StabilisedDenoiserModule),
+             ("burst", burst_settings, BurstDenoiserModule),
+             ("video", video_settings, VideoDenoiserModule))
+
+
 def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None, pixel_shuffle=None, burst=None,
                nlm=None, video=None):
     """bfcnn/__init__.py:81-97: a registry name, a model directory (pipeline.json + weights.npz written by
     `save_model`), or a `.keras` archive of a trained unet_laplacian hydra / the directory holding `model_hydra.keras`
     (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]: a
-    DenoiserModule, or with `self_ensemble` = "d4", "flips" or a sequence of transform numbers 0..7 that module wrapped in a
-    SelfEnsembleDenoiserModule (the mean over the flips and rotations of the image; self_ensemble.py).  `tiled` = True or a dict
-    of TiledDenoiserModule's settings (tile, overlap, margin, tile_batch) wraps that (after any self-ensemble wrapper) in a
-    TiledDenoiserModule: the frame runs as overlapping tiles of one shape (tiling.py).  `pixel_shuffle` = a stride, "auto" (True
-    means "auto") or a dict of PixelShuffleDenoiserModule's settings (stride, max_stride, threshold, refine, replace, seed) wraps
-    that (after the self-ensemble and tiling wrappers) in a PixelShuffleDenoiserModule for noise that is correlated over a few
-    pixels: the sub-images of every s-th pixel run as one batch (pixel_shuffle.py).  `stabilise` = True or a (gain, offset)
-    pair wraps the result (after every other wrapper: the noise fit sees the whole frame) in a
-    StabilisedDenoiserModule for camera noise whose variance is gain x + offset: True fits the pair per frame, a pair fixes it
-    (vst.py).  `burst` = True or a dict of BurstDenoiserModule's settings (reference, levels, search, sigma, k) wraps the result,
-    outermost, in a BurstDenoiserModule: the callable then takes uint8 [B,T,H,W,C] bursts, aligns and merges their frames and
-    denoises the merged frame (burst.py).  `video` = True or a dict of VideoDenoiserModule's settings (n_max, levels, search, sigma,
-    k) wraps the result, outermost, in a VideoDenoiserModule instead: the callable then takes the next uint8 [B,H,W,C] frame of B
-    parallel streams, filters it recursively along the motion and denoises the filtered frame (video.py); together with `burst` a
-    ValueError.  The name "nlm" is no network: it returns a NlmDenoiserModule (non-local means, nlm.py;
-    any channel count 1..4, no weights) under the same wrappers; `nlm` = None or a dict of its settings (sigma, patch, search,
-    strength), a ValueError with any other `model_path`."""
+    DenoiserModule, inside one wrapper for every option of `_WRAPPERS` that is set, in the table's order; each wrapper's module
+    says what its option does and may set:
+
+        self_ensemble  "d4", "flips" or transform numbers 0..7: the mean over flips and rotations of the image (self_ensemble.py)
+        tiled          True or a dict (tile, overlap, margin, tile_batch): the frame runs as overlapping tiles (tiling.py)
+        pixel_shuffle  a stride, "auto" (so is True) or a dict (stride, max_stride, threshold, refine, replace, seed): for noise
+                       correlated over a few pixels, the sub-images of every s-th pixel run as one batch (pixel_shuffle.py)
+        stabilise      True (fitted per frame) or a (gain, offset) pair: camera noise of variance gain x + offset; outside
+                       the three above, so that the noise fit sees the whole frame (vst.py)
+        burst          True or a dict (reference, levels, search, sigma, k): the callable takes uint8 [B,T,H,W,C] bursts,
+                       aligns and merges their frames and denoises the merged frame (burst.py)
+        video          True or a dict (n_max, levels, search, sigma, k): the callable takes the next uint8 [B,H,W,C] frame of B
+                       parallel streams, filters it along the motion and denoises the filtered frame (video.py)
+
+    `burst` and `video` both wrap outermost: both together are a ValueError.  The name "nlm" is no network: it returns a
+    NlmDenoiserModule (non-local means, nlm.py; any channel count 1..4, no weights) under the same wrappers; `nlm` = None or a
+    dict of its settings (sigma, patch, search, strength), a ValueError with any other `model_path`.  Every option is checked
+    before anything is loaded."""
+    options = {"self_ensemble": self_ensemble, "tiled": tiled, "pixel_shuffle": pixel_shuffle, "stabilise": stabilise, "burst": burst,
+               "video": video}
     if nlm is not None and model_path != _nlm.MODEL_NAME:
         raise ValueError(f"nlm sets the non-local means of load_model({_nlm.MODEL_NAME!r}), got it with model_path {model_path!r}")
-    filter_settings = nlm_settings(nlm) if model_path == _nlm.MODEL_NAME else None     # refused before anything is loaded
-    if stabilise is not None and not isinstance(stabilise, (bool, tuple, list)):
-        raise ValueError(f"stabilise must be None, a bool or a (gain, offset) pair, got {stabilise!r}")
-    if stabilise is not None and not isinstance(stabilise, bool):
-        vst._checked_noise_level(stabilise)                      # a bad pair is refused before anything is loaded
-    if tiled is not None and not isinstance(tiled, (bool, dict)):
-        raise ValueError(f"tiled must be None, a bool or a dict of TiledDenoiserModule settings, got {tiled!r}")
-    if isinstance(tiled, dict) and set(tiled) - {"tile", "overlap", "margin", "tile_batch"}:
-        raise ValueError(f"tiled may set tile, overlap, margin and tile_batch, got {sorted(tiled)}")
-    shuffle = pixel_shuffle_settings(pixel_shuffle)              # a bad setting is refused before anything is loaded
-    merge = burst_settings(burst)
-    stream = video_settings(video)
-    if merge is not None and stream is not None:
+    filter_settings = nlm_settings(nlm) if model_path == _nlm.MODEL_NAME else None
+    settings = {keyword: parse(options[keyword]) for keyword, parse, _ in _WRAPPERS}
+    if settings["burst"] is not None and settings["video"] is not None:
         raise ValueError("burst and video both wrap outermost: set one of them")
     module = _load_module(model_path, device) if filter_settings is None else NlmDenoiserModule(**filter_settings)
-    if self_ensemble is not None:
-        module = SelfEnsembleDenoiserModule(module, transforms=self_ensemble)
-    if tiled is not None and tiled is not False:
-        module = TiledDenoiserModule(module, **(tiled if isinstance(tiled, dict) else {}))
-    if shuffle is not None:
-        module = PixelShuffleDenoiserModule(module, **shuffle)
-    if stabilise is not None and stabilise is not False:
-        module = StabilisedDenoiserModule(module, None if stabilise is True else stabilise)
-    if stream is not None:
-        return VideoDenoiserModule(module, **stream)
-    return module if merge is None else BurstDenoiserModule(module, **merge)
+    for keyword, _, wrapper in _WRAPPERS:
+        if settings[keyword] is not None:
+            module = wrapper(module, **settings[keyword])
+    return module
 
 
 def _load_module(model_path: str, device=None) -> DenoiserModule:

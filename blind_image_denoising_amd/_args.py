@@ -113,6 +113,31 @@ def per_image_channel(value, B: int, C: int, what: str) -> torch.Tensor:
     return s.contiguous()
 
 
+def parse_setting(value, option: str, expected: str, settings, check=None, shorthand=None, bools: bool = True):
+    """load_model's `option` as the keyword arguments of its wrapper, None for no wrapper: None | False -> None; True -> {} (the
+    defaults); a dict whose keys are among `settings` -> a copy of it, once check(**it) has passed (its ValueError is prefixed
+    "<option>: ").  With `shorthand`, what is no dict, True included, stands for the dict shorthand(value), or for none where
+    that is None; without `bools` a bool is a wrong type.  Every other value: ValueError "<option> must be <expected>, got ...".  Everything is
+    checked here, before anything is loaded."""
+    if value is None or (bools and value is False):
+        return None
+    given = value
+    if shorthand is not None and not isinstance(value, dict):
+        value = shorthand(value)
+    elif bools and value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError(f"{option} must be {expected}, got {given!r}")
+    if set(value) - set(settings):
+        raise ValueError(f"{option} may set {', '.join(settings)}, got {sorted(value)}")
+    if check is not None:
+        try:
+            check(**value)
+        except ValueError as e:
+            raise ValueError(f"{option}: {e}") from None
+    return dict(value)
+
+
 def module_result(result, dtype, shape, *, hint: str = ""):
     """what a module handed back for a uint8 batch of `shape` is a tensor of `dtype` and that shape; returns it"""
     if not isinstance(result, torch.Tensor) or result.dtype != dtype or tuple(result.shape) != tuple(shape):

@@ -31,8 +31,7 @@ import torch
 
 from . import _args as A
 from . import _native as N
-from .constants import DENOISER_STR
-from .module_denoiser import DenoiserModule, float_form
+from .module_denoiser import DenoiserWrapper
 from .noise_estimate import estimate_noise
 from .pixel_shuffle import pd_merge
 
@@ -98,19 +97,12 @@ def checked_settings(reference: int = 0, levels: int = 3, search: int = 4, sigma
 def parse_setting(burst) -> Optional[dict]:
     """load_model's `burst`: None | False -> None; True -> the defaults; a dict of SETTINGS -> itself.  Everything is checked
     here, before anything is loaded."""
-    if burst is None or burst is False:
-        return None
-    if burst is True:
-        return {}
-    if not isinstance(burst, dict):
-        raise ValueError(f"burst must be None, a bool or a dict of BurstDenoiserModule settings, got {burst!r}")
-    if set(burst) - set(SETTINGS):
-        raise ValueError(f"burst may set {', '.join(SETTINGS)}, got {sorted(burst)}")
-    try:
-        checked_settings(**burst)
-    except ValueError as e:
-        raise ValueError(f"burst: {e}") from None
-    return dict(burst)
+    return A.parse_setting(burst, "burst", "None, a bool or a dict of BurstDenoiserModule settings", SETTINGS, checked_settings)
+
+
+def _check_sigma_batch(sigma, B: int):
+    if isinstance(sigma, torch.Tensor) and tuple(sigma.shape) != (B,):
+        raise ValueError(f"sigma must be None, a float or a [{B}] array for this batch, got shape {tuple(sigma.shape)}")
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------------
@@ -182,6 +174,20 @@ def burst_thresholds(sigma, C: int, k_lo: float = 1.5, k_hi: float = 3.0) -> tor
     return torch.stack([torch.floor(k_lo * E).to(torch.int64), torch.floor(k_hi * E).to(torch.int64) + 1], dim=1).contiguous()
 
 
+def thresholds_of(sigma, k, frame: torch.Tensor) -> torch.Tensor:
+    """burst_thresholds for a uint8 [B,H,W,C] device frame from a checked `sigma` setting: None estimates the level on that
+    frame (estimate_noise, "mad"; no host read), a float is filled in, a [B] tensor is moved to the frame"""
+    B, C = int(frame.shape[0]), int(frame.shape[3])
+    if sigma is None:
+        sigma = estimate_noise(frame.contiguous(), "mad")
+    elif isinstance(sigma, torch.Tensor):
+        _check_sigma_batch(sigma, B)
+        sigma = sigma.to(frame.device)
+    else:
+        sigma = torch.full((B,), sigma, dtype=torch.float64, device=frame.device)
+    return burst_thresholds(sigma, C, *k)
+
+
 def _merge(frames: torch.Tensor, field: torch.Tensor, thresholds: torch.Tensor, ref: int, cast_to_uint8: bool, want_counts: bool):
     B, T, H, W, C = frames.shape
     out = torch.empty((B, H, W, C), dtype=torch.uint8 if cast_to_uint8 else torch.float32, device=frames.device)
@@ -217,12 +223,10 @@ def burst_merge(frames, field: torch.Tensor, thresholds: torch.Tensor, reference
 
 # ---- the wrapper -------------------------------------------------------------------------------------------------------------
 
-class BurstDenoiserModule:
+class BurstDenoiserModule(DenoiserWrapper):
     """A burst merged into one frame, then denoised: uint8 [B,T,H,W,C] -> uint8 [B,H,W,C] (float32, not rounded, with
-    cast_to_uint8=False).  `module`: a DenoiserModule, one of its wrappers (graphed, self-ensemble, stabilised, tiled,
-    pixel-shuffled), any callable that maps a uint8 device tensor [N,H,W,C] to float32 of the same shape -- its float32 form is
-    what runs (module_denoiser.float_form) -- or None for the merge alone.  Same host-or-device input handling, return types and
-    empty-batch behaviour as DenoiserModule.
+    cast_to_uint8=False).  `module`: what every wrapper takes (DenoiserWrapper), or None for the merge alone.  Input handling,
+    return types, empty batches and f16-range status as every wrapper.
 
     A call is: burst_align against frame `reference`, burst_merge to uint8, ONE float denoiser call on the merged [B,H,W,C],
     rounding.  A burst of one frame returns exactly what the wrapped module returns for that frame.  `sigma`: the noise level the
@@ -231,49 +235,16 @@ class BurstDenoiserModule:
     device tensor synchronises: with a fixed sigma the whole call can be captured into a HIP graph.
 
     `last_counts` is the int32 [B,H,W,2] = (den, sq) of the last call of this module or of its float form (None after a burst of
-    one frame): den / 256 frames went into a pixel, and its noise is sigma sqrt(sq) / den.  `last_field` is that call's alignment.
-
-    The f16-range status of the inner call is kept where the wrapped module keeps its own: `check_status` is the wrapped
-    module's, and a host-array call that hits the range switches the model to the exact-fp32 kernels and repeats itself, as a
-    DenoiserModule call does."""
+    one frame): den / 256 frames went into a pixel, and its noise is sigma sqrt(sq) / den.  `last_field` is that call's alignment."""
+    SETTINGS = SETTINGS
 
     def __init__(self, module, reference: int = 0, levels: int = 3, search: int = 4, sigma=None, k=(1.5, 3.0),
                  cast_to_uint8: bool = True):
         if isinstance(module, BurstDenoiserModule):
             raise ValueError("module already merges bursts")
-        self._float = None if module is None else float_form(module)        # ValueError for what is not callable
-        self._module, self._cast_to_uint8 = module, bool(cast_to_uint8)
+        self._wrap(module, cast_to_uint8, allow_none=True)
         self._reference, self._levels, self._search, self._sigma, self._k = checked_settings(reference, levels, search, sigma, k)
-        base = module
-        while base is not None and not isinstance(base, DenoiserModule):
-            base = getattr(base, "_module", None)                 # through the wrappers: whose argument checks and empty output a call uses
-        self._base = base
-        self.name = getattr(module, "name", DENOISER_STR)
-        self._record = {"counts": None, "field": None}            # shared with float_form()
-
-    @property
-    def model_hydra(self):
-        return getattr(self._module, "model_hydra", None)
-
-    @property
-    def reference(self) -> int:
-        return self._reference
-
-    @property
-    def levels(self) -> int:
-        return self._levels
-
-    @property
-    def search(self) -> int:
-        return self._search
-
-    @property
-    def sigma(self):
-        return self._sigma
-
-    @property
-    def k(self) -> Tuple[float, float]:
-        return self._k
+        self._record = {"counts": None, "field": None}
 
     @property
     def last_counts(self) -> Optional[torch.Tensor]:
@@ -283,62 +254,30 @@ class BurstDenoiserModule:
     def last_field(self) -> Optional[torch.Tensor]:
         return self._record["field"]
 
-    def check_status(self, wait: bool = True) -> bool:
-        return self._module.check_status(wait) if hasattr(self._module, "check_status") else True
-
-    def float_form(self) -> "BurstDenoiserModule":
-        """the same pipeline over the same module with the same settings, not rounded; `last_counts` and `last_field` are shared"""
-        inner = BurstDenoiserModule(self._module, self._reference, self._levels, self._search, self._sigma, self._k, cast_to_uint8=False)
-        inner._record = self._record
-        return inner
-
-    def _thresholds(self, frames: torch.Tensor) -> torch.Tensor:
-        B, C = int(frames.shape[0]), int(frames.shape[4])
-        if self._sigma is None:
-            sigma = estimate_noise(frames[:, self._reference].contiguous(), "mad")
-        elif isinstance(self._sigma, torch.Tensor):
-            if tuple(self._sigma.shape) != (B,):
-                raise ValueError(f"sigma must be None, a float or a [{B}] array for this batch, got shape {tuple(self._sigma.shape)}")
-            sigma = self._sigma.to(frames.device)
-        else:
-            sigma = torch.full((B,), self._sigma, dtype=torch.float64, device=frames.device)
-        return burst_thresholds(sigma, C, *self._k)
-
     def __call__(self, frames):
         frames, was_numpy = _checked_frames(frames)
         B, T, H, W, C = frames.shape
         ref = _checked_reference(self._reference, T)
         if self._base is not None:
             self._base._checked_input(frames[:, ref])              # the model's channel count
-        if isinstance(self._sigma, torch.Tensor) and B > 0 and tuple(self._sigma.shape) != (B,):
-            raise ValueError(f"sigma must be None, a float or a [{B}] array for this batch, got shape {tuple(self._sigma.shape)}")
         if B == 0:
-            if self._base is not None:
-                return self._base._empty_output(frames[:, ref], was_numpy)
-            return frames[:, ref].numpy() if was_numpy else frames[:, ref]
+            return self._empty_output(frames[:, ref], was_numpy)
+        _check_sigma_batch(self._sigma, B)
         if T == 1 and self._cast_to_uint8 and callable(getattr(self._module, "float_form", None)):
             return self._module(frames[:, 0].numpy() if was_numpy else frames[:, 0])       # exactly the wrapped module
-        hydra = self.model_hydra
-        if hydra is not None:
-            hydra._require_gpu()
-            frames = frames.to(hydra.device)
-        else:
-            frames = A.to_device(frames, was_numpy, None, "frames", _FEATURE)
-        frames = frames.contiguous()
+        frames = self._place(frames, was_numpy, "frames", _FEATURE)
         to_uint8 = self._cast_to_uint8 or self._module is not None               # the denoiser reads uint8
         if T == 1:
             field = counts = None
             merged = frames[:, 0].contiguous() if to_uint8 else frames[:, 0].float()
         else:
             field = _align(frames, ref, self._levels, self._search)[0]
-            merged, counts = _merge(frames, field, self._thresholds(frames), ref, to_uint8, True)
+            merged, counts = _merge(frames, field, thresholds_of(self._sigma, self._k, frames[:, ref]), ref, to_uint8, True)
         self._record["counts"], self._record["field"] = counts, field
         if self._module is None:
-            return merged.cpu().numpy() if was_numpy else merged
-        result = A.module_result(self._float(merged), torch.float32, merged.shape)
-        if was_numpy and not self.check_status(wait=True):
-            # host arrays are handed back and an activation left the f16 range: the model now runs the exact-fp32 kernels
-            # (check_status switched it); repeat the call
+            return self._deliver(merged, was_numpy)
+        result = self._run(merged)
+        if self._repeat_in_fp32(was_numpy):
             return self(frames.cpu().numpy())
         out = pd_merge(result.to(frames.device), B, H, W, 1, True) if self._cast_to_uint8 else result       # stride 1: the rounding alone
-        return out.cpu().numpy() if was_numpy else out
+        return self._deliver(out, was_numpy)

@@ -1,4 +1,6 @@
 """DenoiserModule: the inference drop-in boundary (bfcnn/module_denoiser.py:15-75)."""
+import operator
+
 import torch
 
 from . import _args as A
@@ -249,3 +251,94 @@ def float_form(module, what: str = "module"):
         raise ValueError(f"{what} must be a DenoiserModule, one of its wrappers (graphed, self-ensemble, stabilised) or a "
                          f"callable uint8 [B,H,W,C] -> float32 [B,H,W,C]")
     return module
+
+
+class DenoiserWrapper:
+    """What every wrapper around a denoiser shares; a wrapper keeps its settings check, its `_record` and the middle of its call.
+
+    `module`: a DenoiserModule, another wrapper, or any callable that maps a uint8 device tensor [N,H,W,C] to float32 of the
+    same shape; its float32 form `_float` is what runs (float_form above).  `_base` is the DenoiserModule at the bottom of the
+    chain of wrappers, None where there is none: a call takes its argument checks (the model's channel count) and its empty
+    output from there, and without one checks a uint8 [B,H,W,C] batch of 1..4 channels and hands an empty batch back as it came.
+    An image is uploaded to the model's device; without a model what came as NumPy goes to the current GPU and a host tensor is
+    refused (_args.to_device).  NumPy in, NumPy out.
+
+    SETTINGS names the wrapper's settings, each kept checked in `_<name>`: they are the read-only attributes of those names and
+    the keyword arguments `float_form()` builds the unrounded twin from.  The twin shares `_record`, where the wrapper has one:
+    a wrapper around this one runs the twin, and `last_*` of either shows the calls of both.
+
+    The f16-range status of the inner calls is kept where the wrapped module keeps its own: `check_status` is the wrapped
+    module's (True where it has none), and a host-array call that hits the range switches the model to the exact-fp32 kernels
+    and repeats itself, as a DenoiserModule call does (`_repeat_in_fp32`)."""
+    SETTINGS = ()
+
+    def __init_subclass__(cls, **kwargs):
+        super().__init_subclass__(**kwargs)
+        for name in cls.SETTINGS:
+            setattr(cls, name, property(operator.attrgetter("_" + name)))
+
+    def _wrap(self, module, cast_to_uint8: bool, allow_none: bool = False):
+        self._float = None if module is None and allow_none else float_form(module)        # ValueError for what is not callable
+        self._module, self._cast_to_uint8 = module, bool(cast_to_uint8)
+        base = module
+        while base is not None and not isinstance(base, DenoiserModule):
+            base = getattr(base, "_module", None)                 # through the wrappers: whose argument checks and empty output a call uses
+        self._base = base
+        self.name = getattr(module, "name", DENOISER_STR)
+
+    @property
+    def model_hydra(self):
+        return getattr(self._module, "model_hydra", None)
+
+    def check_status(self, wait: bool = True) -> bool:
+        return self._module.check_status(wait) if hasattr(self._module, "check_status") else True
+
+    def _settings(self) -> dict:
+        return {name: getattr(self, "_" + name) for name in self.SETTINGS}
+
+    def _twin(self, **settings):
+        return type(self)(self._module, **settings)
+
+    def float_form(self):
+        """this wrapper over the same module with the same settings, not rounded"""
+        inner = self._twin(**self._settings(), cast_to_uint8=False)
+        if hasattr(self, "_record"):
+            inner._record = self._record
+        return inner
+
+    def _checked_input(self, image):
+        """the argument checks of a call: (image as a uint8 [B,H,W,C] torch tensor, whether a numpy array was given)"""
+        if self._base is not None:
+            return self._base._checked_input(image)
+        return A.host_or_device(image, "image", (torch.uint8,), min_hw=0, allow_empty=True)      # no base module: any callable
+
+    def _empty_output(self, image: torch.Tensor, was_numpy: bool):
+        """what a call returns for a batch of no images"""
+        if self._base is not None:
+            return self._base._empty_output(image, was_numpy)
+        return image.numpy() if was_numpy else image
+
+    def _place(self, t: torch.Tensor, was_numpy: bool, what: str, feature: str) -> torch.Tensor:
+        """`t` on the GPU the call runs on, contiguous"""
+        hydra = self.model_hydra
+        if hydra is not None:
+            hydra._require_gpu()
+            t = t.to(hydra.device)
+        else:
+            t = A.to_device(t, was_numpy, None, what, feature)
+        return t.contiguous()
+
+    def _run(self, batch: torch.Tensor) -> torch.Tensor:
+        """the float module on a uint8 device batch"""
+        return A.module_result(self._float(batch), torch.float32, batch.shape)
+
+    def _repeat_in_fp32(self, was_numpy: bool) -> bool:
+        """after an inner call: whether the caller has to `return self(image.cpu().numpy())`.  A call that hands back a host
+        array waits for the inner call's status; when an activation left the f16 range, check_status has switched the model to
+        the exact-fp32 kernels and the call runs again.  Device-tensor calls wait for nothing: their status is the caller's to
+        ask for (`check_status`)."""
+        return was_numpy and not self.check_status(wait=True)
+
+    @staticmethod
+    def _deliver(out: torch.Tensor, was_numpy: bool):
+        return out.cpu().numpy() if was_numpy else out

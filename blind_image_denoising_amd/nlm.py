@@ -28,7 +28,7 @@ import torch
 
 from . import _args as A
 from . import _native as N
-from .constants import DENOISER_STR
+from .module_denoiser import DenoiserWrapper
 from .noise_estimate import estimate_noise
 from .risk import estimate_risk
 
@@ -101,17 +101,7 @@ def checked_settings(sigma=None, patch: int = 1, search: int = 10, strength=0.55
 def parse_setting(nlm) -> dict:
     """load_model's `nlm`: None -> the defaults; a dict of SETTINGS -> itself.  Everything is checked here, before anything is
     loaded."""
-    if nlm is None:
-        return {}
-    if not isinstance(nlm, dict):
-        raise ValueError(f"nlm must be None or a dict of NlmDenoiserModule settings, got {nlm!r}")
-    if set(nlm) - set(SETTINGS):
-        raise ValueError(f"nlm may set {', '.join(SETTINGS)}, got {sorted(nlm)}")
-    try:
-        checked_settings(**nlm)
-    except ValueError as e:
-        raise ValueError(f"nlm: {e}") from None
-    return dict(nlm)
+    return A.parse_setting(nlm, "nlm", "None or a dict of NlmDenoiserModule settings", SETTINGS, checked_settings, bools=False) or {}
 
 
 def _per_image(value, B: int, device, what: str) -> torch.Tensor:
@@ -236,9 +226,10 @@ def nlm_tune(images, sigma=None, strengths=STRENGTHS, patch: int = 1, search: in
 
 # ---- the module --------------------------------------------------------------------------------------------------------------
 
-class NlmDenoiserModule:
+class NlmDenoiserModule(DenoiserWrapper):
     """Non-local means as a denoiser module: uint8 [B,H,W,C] -> uint8 [B,H,W,C] (float32, not rounded, with cast_to_uint8=False),
-    C in 1..4.  Same host-or-device input handling, return types and empty-batch behaviour as DenoiserModule; it has a
+    C in 1..4.  Input handling, return types and empty batches as every wrapper (DenoiserWrapper), around no module: there is no
+    model (`model_hydra` is None) and, in integer arithmetic, no range to leave (`check_status()` is True).  It has a
     `float_form()`, so every wrapper (self-ensemble, tiled, pixel-shuffled, stabilised, burst) and estimate_risk take it.
 
     `sigma`: the noise level the weights are made from; None estimates it per image (estimate_noise, "mad") on the device with
@@ -248,43 +239,19 @@ class NlmDenoiserModule:
 
     `last_weights` is the int32 [B,H,W] = den of the last call of this module or of its float form: den / 4096 is about the
     number of pixels that were averaged, and 1 where the filter found nothing alike (or is off)."""
+    SETTINGS = SETTINGS
 
     def __init__(self, sigma=None, patch: int = 1, search: int = 10, strength=0.55, cast_to_uint8: bool = True):
         self._sigma, self._patch, self._search, self._strength = checked_settings(sigma, patch, search, strength)
-        self._cast_to_uint8 = bool(cast_to_uint8)
-        self.name = DENOISER_STR
-        self._record = {"weights": None}                          # shared with float_form()
+        self._wrap(None, cast_to_uint8, allow_none=True)
+        self._record = {"weights": None}
 
-    model_hydra = None                                            # there is no model: what the wrappers ask first
-
-    @property
-    def sigma(self):
-        return self._sigma
-
-    @property
-    def patch(self) -> int:
-        return self._patch
-
-    @property
-    def search(self) -> int:
-        return self._search
-
-    @property
-    def strength(self):
-        return self._strength
+    def _twin(self, **settings):
+        return type(self)(**settings)                             # no module to pass on
 
     @property
     def last_weights(self) -> Optional[torch.Tensor]:
         return self._record["weights"]
-
-    def check_status(self, wait: bool = True) -> bool:
-        return True                                               # integer arithmetic: there is no range to leave
-
-    def float_form(self) -> "NlmDenoiserModule":
-        """the same filter with the same settings, not rounded; `last_weights` is shared"""
-        inner = NlmDenoiserModule(self._sigma, self._patch, self._search, self._strength, cast_to_uint8=False)
-        inner._record = self._record
-        return inner
 
     def __call__(self, images):
         images, was_numpy = _checked_images(images, "image")
@@ -293,8 +260,8 @@ class NlmDenoiserModule:
             if isinstance(value, torch.Tensor) and B > 0 and tuple(value.shape) != (B,):
                 raise ValueError(f"{what} must be a float or a [{B}] array for this batch, got shape {tuple(value.shape)}")
         if B == 0:
-            return images.numpy() if was_numpy else images
-        images = A.to_device(images, was_numpy, None, "image", _FEATURE).contiguous()
+            return self._empty_output(images, was_numpy)
+        images = self._place(images, was_numpy, "image", _FEATURE)
         sigma = estimate_noise(images, "mad") if self._sigma is None else _per_image(self._sigma, B, images.device, "sigma")
         if isinstance(self._strength, str):
             strength = _tune(images, sigma, STRENGTHS, self._patch, self._search, 2, 1, 0)[0]
@@ -302,4 +269,4 @@ class NlmDenoiserModule:
             strength = self._strength
         out, weights = _launch(images, nlm_params(sigma, C, self._patch, strength), self._patch, self._search, self._cast_to_uint8, True)
         self._record["weights"] = weights
-        return out.cpu().numpy() if was_numpy else out
+        return self._deliver(out, was_numpy)

@@ -30,8 +30,7 @@ import torch
 
 from . import _args as A
 from . import _native as N
-from .constants import DENOISER_STR
-from .module_denoiser import DenoiserModule, float_form
+from .module_denoiser import DenoiserWrapper
 
 _FEATURE = "the pixel-shuffle code"
 MAX_STRIDE = 8                  # of every kernel here
@@ -203,32 +202,16 @@ def checked_settings(stride: Union[int, str] = 2, max_stride: int = 4, threshold
 def parse_setting(pixel_shuffle) -> Optional[dict]:
     """load_model's `pixel_shuffle`: None | False -> None; True -> "auto"; an int or "auto" -> that stride; a dict of SETTINGS ->
     itself.  Everything is checked here, before anything is loaded."""
-    if pixel_shuffle is None or pixel_shuffle is False:
-        return None
-    if pixel_shuffle is True:
-        pixel_shuffle = "auto"
-    if isinstance(pixel_shuffle, dict):
-        if set(pixel_shuffle) - set(SETTINGS):
-            raise ValueError(f"pixel_shuffle may set {', '.join(SETTINGS)}, got {sorted(pixel_shuffle)}")
-        settings = dict(pixel_shuffle)
-    elif isinstance(pixel_shuffle, (int, str)):
-        settings = {"stride": pixel_shuffle}
-    else:
-        raise ValueError(f'pixel_shuffle must be None, a bool, a stride, "auto" or a dict of PixelShuffleDenoiserModule settings, '
-                         f"got {pixel_shuffle!r}")
-    try:
-        checked_settings(**settings)
-    except ValueError as e:
-        raise ValueError(f"pixel_shuffle: {e}") from None
-    return settings
+    def stride_of(value):
+        return {"stride": "auto" if value is True else value} if isinstance(value, (int, str)) else None
+    return A.parse_setting(pixel_shuffle, "pixel_shuffle", 'None, a bool, a stride, "auto" or a dict of PixelShuffleDenoiserModule settings',
+                           SETTINGS, checked_settings, stride_of)
 
 
-class PixelShuffleDenoiserModule:
+class PixelShuffleDenoiserModule(DenoiserWrapper):
     """A denoiser run on the s^2 sub-images of every s-th pixel, whose noise is correlated over 1 / s of the distance: uint8
-    [B,H,W,C] -> uint8 [B,H,W,C] (float32, not rounded, with cast_to_uint8=False).  `module`: a DenoiserModule, one of its wrappers,
-    or any callable that maps a uint8 device tensor [N,H,W,C] to float32 of the same shape; its float32 form is what runs
-    (module_denoiser.float_form).  Same argument checks, host-or-device input handling, return types and empty-batch behaviour
-    as DenoiserModule.
+    [B,H,W,C] -> uint8 [B,H,W,C] (float32, not rounded, with cast_to_uint8=False).  `module`, argument checks, input handling,
+    return types, empty batches and f16-range status as every wrapper (DenoiserWrapper).
 
     A call is: pd_split_u8, ONE float denoiser call on [B s^2, Hs, Ws, C], pd_merge.  With `refine` = T > 0 the merged result is
     rounded to uint8, pd_replace_u8 makes T copies of it in which a share `replace` of the pixels carries the noisy input again
@@ -241,79 +224,22 @@ class PixelShuffleDenoiserModule:
     fixed stride has none.  The probe cannot tell correlated noise from fine texture of the image itself, which also rises with s:
     "auto" is for frames whose noise is well above their pixel-scale texture.  `last_stride` is what the last
     call of this module or of its float form used.  A stride of 1 with
-    refine=0 returns exactly what the wrapped module returns.
-
-    The f16-range status of the inner calls is kept where the wrapped module keeps its own: `check_status` is the wrapped
-    module's, and a host-array call that hits the range switches the model to the exact-fp32 kernels and repeats itself, as a
-    DenoiserModule call does."""
+    refine=0 returns exactly what the wrapped module returns."""
+    SETTINGS = SETTINGS
 
     def __init__(self, module, stride: Union[int, str] = 2, max_stride: int = 4, threshold: float = 0.8, refine: int = 0,
                  replace: float = 0.16, seed: int = 0, cast_to_uint8: bool = True):
         if isinstance(module, PixelShuffleDenoiserModule):
             raise ValueError("module is already pixel-shuffled")
-        self._float = float_form(module)                          # ValueError for what is not callable
-        self._module, self._cast_to_uint8 = module, bool(cast_to_uint8)
+        self._wrap(module, cast_to_uint8)
         (self._stride, self._max_stride, self._threshold, self._refine, self._replace,
          self._seed) = checked_settings(stride, max_stride, threshold, refine, replace, seed)
-        base = module
-        while base is not None and not isinstance(base, DenoiserModule):
-            base = getattr(base, "_module", None)                 # through the wrappers: whose argument checks and empty output a call uses
-        self._base = base
-        self.name = getattr(module, "name", DENOISER_STR)
-        self._record = {"stride": None}                           # shared with float_form(): a wrapper around this module runs that
-
-    @property
-    def model_hydra(self):
-        return getattr(self._module, "model_hydra", None)
+        self._record = {"stride": None}
 
     @property
     def last_stride(self) -> Optional[int]:
         """the stride of the last call of this module or of its float form"""
         return self._record["stride"]
-
-    @property
-    def stride(self) -> Union[int, str]:
-        return self._stride
-
-    @property
-    def max_stride(self) -> int:
-        return self._max_stride
-
-    @property
-    def threshold(self) -> float:
-        return self._threshold
-
-    @property
-    def refine(self) -> int:
-        return self._refine
-
-    @property
-    def replace(self) -> float:
-        return self._replace
-
-    @property
-    def seed(self) -> int:
-        return self._seed
-
-    def check_status(self, wait: bool = True) -> bool:
-        return self._module.check_status(wait) if hasattr(self._module, "check_status") else True
-
-    def float_form(self) -> "PixelShuffleDenoiserModule":
-        """the same pipeline over the same module with the same settings, merged (or averaged) but not rounded; `last_stride` is shared"""
-        inner = PixelShuffleDenoiserModule(self._module, self._stride, self._max_stride, self._threshold, self._refine, self._replace,
-                                           self._seed, cast_to_uint8=False)
-        inner._record = self._record
-        return inner
-
-    def _checked_input(self, image):
-        if self._base is not None:
-            return self._base._checked_input(image)
-        return A.host_or_device(image, "image", (torch.uint8,), min_hw=0, allow_empty=True)      # no base module: any callable
-
-    def _empty_output(self, image: torch.Tensor, was_numpy: bool):
-        if self._base is not None:
-            return self._base._empty_output(image, was_numpy)
-        return image.numpy() if was_numpy else image
 
     def _stride_for(self, image: torch.Tensor) -> int:
         H, W = int(image.shape[1]), int(image.shape[2])
@@ -332,25 +258,15 @@ class PixelShuffleDenoiserModule:
             return self._empty_output(image, was_numpy)
         if self._stride != "auto":
             _checked_stride(self._stride, H, W)                   # before the GPU is touched
-        hydra = self.model_hydra
-        if hydra is not None:
-            hydra._require_gpu()
-            image = image.to(hydra.device)
-        else:
-            image = A.to_device(image, was_numpy, None, "image", _FEATURE)
-        image = image.contiguous()
+        image = self._place(image, was_numpy, "image", _FEATURE)
         s = self._record["stride"] = self._stride_for(image)
-        members = pd_split_u8(image, s)
-        result = A.module_result(self._float(members), torch.float32, members.shape)
-        if was_numpy and not self.check_status(wait=True):
-            # host arrays are handed back and an activation left the f16 range: the model now runs the exact-fp32 kernels
-            # (check_status switched it); repeat the call
+        result = self._run(pd_split_u8(image, s))
+        if self._repeat_in_fp32(was_numpy):
             return self(image.cpu().numpy())
         out = pd_merge(result.to(image.device), B, H, W, s, self._cast_to_uint8 or self._refine > 0)
         if self._refine > 0:
-            copies = pd_replace_u8(out, image, self._refine, self._replace, self._seed)
-            result = A.module_result(self._float(copies), torch.float32, copies.shape)
-            if was_numpy and not self.check_status(wait=True):
+            result = self._run(pd_replace_u8(out, image, self._refine, self._replace, self._seed))
+            if self._repeat_in_fp32(was_numpy):
                 return self(image.cpu().numpy())
             out = pd_mean(result.to(image.device), self._refine, self._cast_to_uint8)
-        return out.cpu().numpy() if was_numpy else out
+        return self._deliver(out, was_numpy)

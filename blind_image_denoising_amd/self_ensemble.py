@@ -17,7 +17,7 @@ import torch
 
 from . import _args as A
 from . import _native as N
-from .module_denoiser import DenoiserModule, float_form
+from .module_denoiser import DenoiserModule, DenoiserWrapper
 
 TRANSFORM_SETS = {"d4": (0, 1, 2, 3, 4, 5, 6, 7), "flips": (0, 2, 4, 6)}
 _FEATURE = "the dihedral transform"
@@ -112,59 +112,41 @@ def dihedral_merge(even_f32: Optional[torch.Tensor], odd_f32: Optional[torch.Ten
     return out
 
 
-class SelfEnsembleDenoiserModule:
+def parse_setting(self_ensemble) -> Optional[dict]:
+    """load_model's `self_ensemble`: None -> None; everything parse_transforms takes -> those transforms.  Checked here, before
+    anything is loaded."""
+    return None if self_ensemble is None else {"transforms": parse_transforms(self_ensemble)}
+
+
+class SelfEnsembleDenoiserModule(DenoiserWrapper):
     """A DenoiserModule run on the members T_k of the image, k in `transforms`, and averaged: uint8 [B,H,W,C] -> uint8 [B,H,W,C]
-    (float32, not rounded, with cast_to_uint8=False).  Same argument checks, host-or-device input handling, return types and
-    empty-batch behaviour as DenoiserModule (they are its own).
+    (float32, not rounded, with cast_to_uint8=False).  Argument checks, input handling, return types and f16-range status as
+    every wrapper (DenoiserWrapper); the module itself must be a DenoiserModule.
 
     A call is: dihedral_stack_u8, one call of DenoiserModule(hydra, cast_to_uint8=False) per batch of members, dihedral_merge.
     Batching contract: for H == W every member goes through ONE hydra call on [n*B, H, W, C], member-major in ascending k;
     otherwise the even members go through one call on [n_even*B, H, W, C] and the odd ones through another on [n_odd*B, W, H, C]
     (a batch with no members is not called).  The merge adds the members' results in ascending k, sequentially in fp32, divides by
-    their number and rounds half to even: `transforms=[0]` returns exactly what DenoiserModule(hydra, cast_to_uint8) returns.
-
-    The f16-range status of the inner calls is kept where the wrapped module keeps its own: `check_status` is the wrapped
-    module's, and a host-array call that hits the range switches the model to the exact-fp32 kernels and repeats itself, as a
-    DenoiserModule call does."""
+    their number and rounds half to even: `transforms=[0]` returns exactly what DenoiserModule(hydra, cast_to_uint8) returns."""
+    SETTINGS = ("transforms",)
 
     def __init__(self, module: DenoiserModule, transforms="d4", cast_to_uint8: bool = True):
         if not isinstance(module, DenoiserModule):
             raise ValueError("module must be a DenoiserModule")
         self._transforms = parse_transforms(transforms)
-        self._module, self._cast_to_uint8 = module, bool(cast_to_uint8)
-        self._inner = float_form(module)                # shares the status record: check_status() below sees the inner calls
-        self.name = module.name
-
-    @property
-    def model_hydra(self):
-        return self._module.model_hydra
-
-    @property
-    def transforms(self) -> Tuple[int, ...]:
-        return self._transforms
-
-    def check_status(self, wait: bool = True) -> bool:
-        return self._module.check_status(wait)
-
-    def float_form(self) -> "SelfEnsembleDenoiserModule":
-        """the same ensemble over the same module, averaged but not rounded"""
-        return SelfEnsembleDenoiserModule(self._module, self._transforms, cast_to_uint8=False)
+        self._wrap(module, cast_to_uint8)
+        self._inner = self._float                       # shares the status record: check_status() sees the inner calls
 
     def __call__(self, image):
-        image, was_numpy = self._module._checked_input(image)
+        image, was_numpy = self._checked_input(image)
         if image.shape[0] == 0:
-            return self._module._empty_output(image, was_numpy)
-        hydra = self.model_hydra
-        hydra._require_gpu()
-        image = image.to(hydra.device).contiguous()
+            return self._empty_output(image, was_numpy)
+        image = self._place(image, was_numpy, "image", _FEATURE)
         B, H, W, _ = image.shape
         batches = dihedral_stack_u8(image, self._transforms, joint=H == W)
         results = []
         for batch in batches:
             results.append(None if batch is None else self._inner(batch))
-            if was_numpy and batch is not None and not self.check_status(wait=True):
-                # host arrays are handed back and an activation left the f16 range: the model now runs the exact-fp32 kernels
-                # (check_status switched it); repeat the call
+            if batch is not None and self._repeat_in_fp32(was_numpy):
                 return self(image.cpu().numpy())
-        out = dihedral_merge(results[0], results[1], self._transforms, B, H, W, self._cast_to_uint8)
-        return out.cpu().numpy() if was_numpy else out
+        return self._deliver(dihedral_merge(results[0], results[1], self._transforms, B, H, W, self._cast_to_uint8), was_numpy)

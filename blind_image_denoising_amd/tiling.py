@@ -22,11 +22,11 @@ import torch
 
 from . import _args as A
 from . import _native as N
-from .constants import DENOISER_STR
 from .model import HydraModel
-from .module_denoiser import DenoiserModule, float_form
+from .module_denoiser import DenoiserWrapper
 
 _FEATURE = "the tiling code"
+SETTINGS = ("tile", "overlap", "margin", "tile_batch")
 DEFAULT_MARGIN = 8              # of a model without a finite receptive field (attention, pyramids): a guard band, not exactness
 
 
@@ -133,11 +133,36 @@ def default_overlap(tile: int, margin: int) -> int:
     return min(tile // 2, max(32, 2 * margin + 16))
 
 
-class TiledDenoiserModule:
+def checked_settings(tile: int = 256, overlap: Optional[int] = None, margin: Optional[int] = None, tile_batch: int = 16):
+    """the settings of TiledDenoiserModule, checked: (tile, overlap, margin, tile_batch).  A margin of None is the model's own,
+    known once there is a model: it stays None, and so does an overlap that follows from it."""
+    tile, tile_batch = A.int_in(tile, "tile", 1), A.int_in(tile_batch, "tile_batch", 1)
+    if margin is None:
+        if overlap is not None:
+            overlap = _checked_plan_arguments(tile, overlap, 0)[1]
+        return tile, overlap, None, tile_batch
+    margin = A.int_in(margin, "margin", 0)
+    if 2 * margin > tile // 2:
+        raise ValueError(f"margin {margin} needs 2 * margin <= tile // 2: the smallest tile that works is {4 * margin}, got {tile}")
+    overlap = default_overlap(tile, margin) if overlap is None else overlap
+    return _checked_plan_arguments(tile, overlap, margin) + (tile_batch,)
+
+
+def parse_setting(tiled) -> Optional[dict]:
+    """load_model's `tiled`: None | False -> None; True -> the defaults; a dict of SETTINGS -> itself.  Everything that does not
+    depend on the model is checked here, before anything is loaded."""
+    if isinstance(tiled, dict) and set(tiled) - set(SETTINGS):
+        raise ValueError(f"tiled may set tile, overlap, margin and tile_batch, got {sorted(tiled)}")
+    settings = A.parse_setting(tiled, "tiled", "None, a bool or a dict of TiledDenoiserModule settings", SETTINGS)
+    if settings:
+        checked_settings(**settings)
+    return settings
+
+
+class TiledDenoiserModule(DenoiserWrapper):
     """A denoiser run tile by tile: uint8 [B,H,W,C] -> uint8 [B,H,W,C] (float32, not rounded, with cast_to_uint8=False).
-    `module`: a DenoiserModule, one of its wrappers, or any callable that maps a uint8 device tensor [N,H,W,C] to float32 of the
-    same shape; its float32 form is what runs (module_denoiser.float_form).  Same argument checks, host-or-device input
-    handling, return types and empty-batch behaviour as DenoiserModule.
+    `module`, argument checks, input handling, return types, empty batches and f16-range status as every wrapper
+    (DenoiserWrapper).
 
     `margin` defaults to receptive_radius(model) -- with it a tile's weighted pixels never saw the cut, and the 16-filter resnet
     gives what it gives on the whole frame wherever the frame's own padding does not reach -- or to 8 where
@@ -146,77 +171,24 @@ class TiledDenoiserModule:
     Batching contract: with N = B ny nx tiles and K = min(tile_batch, N), the chunks start at tiles 0, K, 2K, ... and the last
     one at N - K (it is shifted back and computes a few tiles again), so that every denoiser call has the shape [K, t_h, t_w, C]
     and every slot of it holds a real tile.  Each chunk is tile_split_u8, the float module, a store into the results
-    [N, t_h, t_w, C]; one tile_blend follows.  `last_plan` is the TilePlan of the last call.
-
-    The f16-range status of the inner calls is kept where the wrapped module keeps its own: `check_status` is the wrapped
-    module's, and a host-array call that hits the range switches the model to the exact-fp32 kernels and repeats itself, as a
-    DenoiserModule call does."""
+    [N, t_h, t_w, C]; one tile_blend follows.  `last_plan` is the TilePlan of the last call."""
+    SETTINGS = SETTINGS
 
     def __init__(self, module, tile: int = 256, overlap: Optional[int] = None, margin: Optional[int] = None, tile_batch: int = 16,
                  cast_to_uint8: bool = True):
         if isinstance(module, TiledDenoiserModule):
             raise ValueError("module is already tiled")
-        self._float = float_form(module)                          # ValueError for what is not callable
-        self._module, self._cast_to_uint8 = module, bool(cast_to_uint8)
-        self._tile = A.int_in(tile, "tile", 1)
-        self._tile_batch = A.int_in(tile_batch, "tile_batch", 1)
+        self._wrap(module, cast_to_uint8)
         if margin is None:
             radius = receptive_radius(self.model_hydra)
             margin = DEFAULT_MARGIN if radius is None else radius
-        self._margin = A.int_in(margin, "margin", 0)
-        if 2 * self._margin > self._tile // 2:
-            raise ValueError(f"margin {self._margin} needs 2 * margin <= tile // 2: the smallest tile that works is "
-                             f"{4 * self._margin}, got {self._tile}")
-        self._overlap = default_overlap(self._tile, self._margin) if overlap is None else overlap
-        self._tile, self._overlap, self._margin = _checked_plan_arguments(self._tile, self._overlap, self._margin)
-        base = module if isinstance(module, DenoiserModule) else getattr(module, "_module", None)
-        self._base = base if isinstance(base, DenoiserModule) else None      # whose argument checks and empty output a call uses
-        self.name = getattr(module, "name", DENOISER_STR)
-        self._record = {"plan": None}                             # shared with float_form(): a wrapper around this module runs that
-
-    @property
-    def model_hydra(self):
-        return getattr(self._module, "model_hydra", None)
+        self._tile, self._overlap, self._margin, self._tile_batch = checked_settings(tile, overlap, margin, tile_batch)
+        self._record = {"plan": None}
 
     @property
     def last_plan(self) -> Optional[TilePlan]:
         """the TilePlan of the last call of this module or of its float form"""
         return self._record["plan"]
-
-    @property
-    def tile(self) -> int:
-        return self._tile
-
-    @property
-    def overlap(self) -> int:
-        return self._overlap
-
-    @property
-    def margin(self) -> int:
-        return self._margin
-
-    @property
-    def tile_batch(self) -> int:
-        return self._tile_batch
-
-    def check_status(self, wait: bool = True) -> bool:
-        return self._module.check_status(wait) if hasattr(self._module, "check_status") else True
-
-    def float_form(self) -> "TiledDenoiserModule":
-        """the same tiling of the same module with the same settings, blended but not rounded; `last_plan` is shared"""
-        inner = TiledDenoiserModule(self._module, self._tile, self._overlap, self._margin, self._tile_batch, cast_to_uint8=False)
-        inner._record = self._record
-        return inner
-
-    def _checked_input(self, image):
-        if self._base is not None:
-            return self._base._checked_input(image)
-        return A.host_or_device(image, "image", (torch.uint8,), min_hw=0, allow_empty=True)      # no base module: any callable
-
-    def _empty_output(self, image: torch.Tensor, was_numpy: bool):
-        if self._base is not None:
-            return self._base._empty_output(image, was_numpy)
-        return image.numpy() if was_numpy else image
 
     @staticmethod
     def chunk_starts(tiles: int, tile_batch: int):
@@ -232,25 +204,16 @@ class TiledDenoiserModule:
         B, H, W, _ = image.shape
         if B == 0:
             return self._empty_output(image, was_numpy)
-        hydra = self.model_hydra
-        if hydra is not None:
-            hydra._require_gpu()
-            image = image.to(hydra.device)
-        else:
-            image = A.to_device(image, was_numpy, None, "image", _FEATURE)
-        image = image.contiguous()
+        image = self._place(image, was_numpy, "image", _FEATURE)
         plan = self._record["plan"] = tile_plan(H, W, self._tile, self._overlap, self._margin)
         K, starts = self.chunk_starts(B * plan.tiles, self._tile_batch)
         results = None
         for start in starts:
             batch = tile_split_u8(image, self._tile, self._overlap, start, K)
-            result = A.module_result(self._float(batch), torch.float32, batch.shape)
-            if was_numpy and not self.check_status(wait=True):
-                # host arrays are handed back and an activation left the f16 range: the model now runs the exact-fp32 kernels
-                # (check_status switched it); repeat the call
+            result = self._run(batch)
+            if self._repeat_in_fp32(was_numpy):
                 return self(image.cpu().numpy())
             if results is None:
                 results = torch.empty((B * plan.tiles,) + tuple(result.shape[1:]), dtype=torch.float32, device=image.device)
             results[start:start + K].copy_(result)
-        out = tile_blend(results, B, H, W, self._tile, self._overlap, self._margin, self._cast_to_uint8)
-        return out.cpu().numpy() if was_numpy else out
+        return self._deliver(tile_blend(results, B, H, W, self._tile, self._overlap, self._margin, self._cast_to_uint8), was_numpy)

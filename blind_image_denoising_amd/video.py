@@ -17,7 +17,7 @@ For a frame x, a field d on the 16 x 16 tiles of burst.py, thresholds (lo, hi) a
 
 An empty state passes the first frame through, n_max = 1 passes every frame through, identical frames keep acc = 256 x while cnt
 climbs to 256 n_max, and in the steady state a new frame has weight 1 / n_max.  There is no CPU execution path for the kernels."""
-from typing import NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -25,9 +25,7 @@ import torch
 from . import _args as A
 from . import _native as N
 from . import burst as BU
-from .constants import DENOISER_STR
-from .module_denoiser import DenoiserModule, float_form
-from .noise_estimate import estimate_noise
+from .module_denoiser import DenoiserWrapper
 from .pixel_shuffle import pd_merge
 
 _FEATURE = "the video code"
@@ -53,19 +51,7 @@ def checked_settings(n_max: int = 8, levels: int = 3, search: int = 4, sigma=Non
 def parse_setting(video) -> Optional[dict]:
     """load_model's `video`: None | False -> None; True -> the defaults; a dict of SETTINGS -> itself.  Everything is checked
     here, before anything is loaded."""
-    if video is None or video is False:
-        return None
-    if video is True:
-        return {}
-    if not isinstance(video, dict):
-        raise ValueError(f"video must be None, a bool or a dict of VideoDenoiserModule settings, got {video!r}")
-    if set(video) - set(SETTINGS):
-        raise ValueError(f"video may set {', '.join(SETTINGS)}, got {sorted(video)}")
-    try:
-        checked_settings(**video)
-    except ValueError as e:
-        raise ValueError(f"video: {e}") from None
-    return dict(video)
+    return A.parse_setting(video, "video", "None, a bool or a dict of VideoDenoiserModule settings", SETTINGS, checked_settings)
 
 
 def _checked_state(state, shape, device) -> VideoState:
@@ -128,11 +114,10 @@ def video_update(x, state: VideoState, field: torch.Tensor, thresholds: torch.Te
 
 # ---- the wrapper -------------------------------------------------------------------------------------------------------------
 
-class VideoDenoiserModule:
+class VideoDenoiserModule(DenoiserWrapper):
     """The next frame of B parallel streams, temporally filtered, then denoised: uint8 [B,H,W,C] -> uint8 [B,H,W,C] (float32, not
-    rounded, with cast_to_uint8=False).  `module`: everything BurstDenoiserModule takes (a DenoiserModule, one of its wrappers, any
-    callable uint8 device tensor [N,H,W,C] -> float32 of the same shape -- its float32 form is what runs) or None for the temporal
-    filter alone; a burst or video wrapper is refused.  Same host-or-device input handling and return types as DenoiserModule.
+    rounded, with cast_to_uint8=False).  `module`: what every wrapper takes (DenoiserWrapper), or None for the temporal filter
+    alone; a burst or video wrapper is refused.  Input handling, return types and empty batches as every wrapper.
 
     A call is: burst_align of the state's image against the frame, video_update with thresholds from burst_thresholds, ONE float
     denoiser call on the new state's uint8 image, rounding.  The first frame after reset(), and every frame with n_max = 1, returns
@@ -146,43 +131,14 @@ class VideoDenoiserModule:
     pixel), `last_field` that call's alignment, `state` the VideoState.  `check_status` is the wrapped module's; a host-array call
     that hits the f16 range switches the model to the exact-fp32 kernels and repeats the denoiser on the same filtered frame: the
     state advances once."""
+    SETTINGS = SETTINGS
 
     def __init__(self, module, n_max: int = 8, levels: int = 3, search: int = 4, sigma=None, k=(1.5, 3.0), cast_to_uint8: bool = True):
         if isinstance(module, (BU.BurstDenoiserModule, VideoDenoiserModule)):
             raise ValueError("module already merges frames: a burst or video wrapper goes outermost")
-        self._float = None if module is None else float_form(module)        # ValueError for what is not callable
-        self._module, self._cast_to_uint8 = module, bool(cast_to_uint8)
+        self._wrap(module, cast_to_uint8, allow_none=True)
         self._n_max, self._levels, self._search, self._sigma, self._k = checked_settings(n_max, levels, search, sigma, k)
-        base = module
-        while base is not None and not isinstance(base, DenoiserModule):
-            base = getattr(base, "_module", None)                 # through the wrappers: whose argument checks and empty output a call uses
-        self._base = base
-        self.name = getattr(module, "name", DENOISER_STR)
-        self._record = {"state": None, "field": None, "captured": []}          # shared with float_form()
-
-    @property
-    def model_hydra(self):
-        return getattr(self._module, "model_hydra", None)
-
-    @property
-    def n_max(self) -> int:
-        return self._n_max
-
-    @property
-    def levels(self) -> int:
-        return self._levels
-
-    @property
-    def search(self) -> int:
-        return self._search
-
-    @property
-    def sigma(self):
-        return self._sigma
-
-    @property
-    def k(self) -> Tuple[float, float]:
-        return self._k
+        self._record = {"state": None, "field": None, "captured": []}          # float_form() shares it: the STATE too
 
     @property
     def state(self) -> Optional[VideoState]:
@@ -200,43 +156,17 @@ class VideoDenoiserModule:
         """empties the state: the next frame passes the temporal filter unchanged, and may have another shape"""
         self._record["state"] = self._record["field"] = None
 
-    def check_status(self, wait: bool = True) -> bool:
-        return self._module.check_status(wait) if hasattr(self._module, "check_status") else True
-
-    def float_form(self) -> "VideoDenoiserModule":
-        """the same pipeline over the same module, settings and STATE, not rounded"""
-        inner = VideoDenoiserModule(self._module, self._n_max, self._levels, self._search, self._sigma, self._k, cast_to_uint8=False)
-        inner._record = self._record
-        return inner
-
-    def _thresholds(self, x: torch.Tensor) -> torch.Tensor:
-        B, C = int(x.shape[0]), int(x.shape[3])
-        if self._sigma is None:
-            sigma = estimate_noise(x, "mad")
-        elif isinstance(self._sigma, torch.Tensor):
-            sigma = self._sigma.to(x.device)
-        else:
-            sigma = torch.full((B,), self._sigma, dtype=torch.float64, device=x.device)
-        return BU.burst_thresholds(sigma, C, *self._k)
-
     def _checked_frame(self, x, what: str = "frame"):
         x, was_numpy = A.host_or_device(x, what, (torch.uint8,), allow_empty=True)
         if self._base is not None:
             self._base._checked_input(x)                          # the model's channel count
         B = int(x.shape[0])
-        if isinstance(self._sigma, torch.Tensor) and B > 0 and tuple(self._sigma.shape) != (B,):
-            raise ValueError(f"sigma must be None, a float or a [{B}] array for this batch, got shape {tuple(self._sigma.shape)}")
+        if B > 0:
+            BU._check_sigma_batch(self._sigma, B)
         state = self._record["state"]
         if state is not None and B > 0 and tuple(state.acc.shape) != tuple(x.shape):
             raise ValueError(f"the state holds streams of shape {tuple(state.acc.shape)}, got a {what} of {tuple(x.shape)}: reset() first")
         return x, was_numpy
-
-    def _to_device(self, x: torch.Tensor, was_numpy: bool) -> torch.Tensor:
-        hydra = self.model_hydra
-        if hydra is not None:
-            hydra._require_gpu()
-            return x.to(hydra.device).contiguous()
-        return A.to_device(x, was_numpy, None, "frame", _FEATURE).contiguous()
 
     def _filter(self, x: torch.Tensor, to_uint8: bool) -> torch.Tensor:
         """the temporal step on a contiguous device frame: advances the state, returns the filtered frame"""
@@ -251,17 +181,17 @@ class VideoDenoiserModule:
             # keep it for the life of the module (reset() does not drop it), or the allocator hands its memory to the next tensor
             self._record["captured"].append(state)
         field = BU._align(torch.stack([x, state.image], dim=1), 0, self._levels, self._search)[0][:, 1].contiguous()
-        out, state = _update(x, state, field, self._thresholds(x), self._n_max, to_uint8)
+        out, state = _update(x, state, field, BU.thresholds_of(self._sigma, self._k, x), self._n_max, to_uint8)
         self._record["state"], self._record["field"] = state, field
         return out
 
     def _denoise(self, filtered: torch.Tensor, wait: bool) -> torch.Tensor:
         """the float denoiser on the filtered uint8 frame; with `wait` the f16-range repeat of a host-array call"""
-        result = A.module_result(self._float(filtered), torch.float32, filtered.shape)
+        result = self._run(filtered)
         if wait and not self.check_status(wait=True):
             # an activation left the f16 range: the model now runs the exact-fp32 kernels (check_status switched it).  Repeat the
-            # denoiser on the same filtered frame: the state has advanced once
-            result = A.module_result(self._float(filtered), torch.float32, filtered.shape)
+            # denoiser on the same filtered frame, not the call: the state has advanced once
+            result = self._run(filtered)
             self.check_status(wait=True)
         return result
 
@@ -269,16 +199,14 @@ class VideoDenoiserModule:
         x, was_numpy = self._checked_frame(frame)
         B, H, W, C = x.shape
         if B == 0:
-            if self._base is not None:
-                return self._base._empty_output(x, was_numpy)
-            return x.numpy() if was_numpy else x
-        x = self._to_device(x, was_numpy)
+            return self._empty_output(x, was_numpy)
+        x = self._place(x, was_numpy, "frame", _FEATURE)
         filtered = self._filter(x, self._cast_to_uint8 or self._module is not None)          # the denoiser reads uint8
         if self._module is None:
-            return filtered.cpu().numpy() if was_numpy else filtered
+            return self._deliver(filtered, was_numpy)
         result = self._denoise(filtered, was_numpy)
         out = pd_merge(result.to(x.device), B, H, W, 1, True) if self._cast_to_uint8 else result        # stride 1: the rounding alone
-        return out.cpu().numpy() if was_numpy else out
+        return self._deliver(out, was_numpy)
 
     def denoise_sequence(self, frames):
         """reset(), then the T frames of uint8 [B,T,H,W,C] (torch on the GPU, or NumPy, which is uploaded once) one after the other:
@@ -294,13 +222,12 @@ class VideoDenoiserModule:
         if B == 0:
             out = torch.empty((0, T, H, W, C), dtype=torch.uint8 if self._cast_to_uint8 else torch.float32)
             return out.numpy() if was_numpy else out
-        frames = self._to_device(frames, was_numpy)
+        frames = self._place(frames, was_numpy, "frame", _FEATURE)
         outs = [self(frames[:, t].contiguous()) for t in range(T)]
         if was_numpy and not self.check_status(wait=True):
-            # host arrays are handed back and an activation left the f16 range somewhere in the sequence: the model now runs the
-            # exact-fp32 kernels; run the sequence again from the empty state
+            # an activation left the f16 range somewhere in the sequence: the model now runs the exact-fp32 kernels; run the
+            # sequence again from the empty state
             self.reset()
             outs = [self(frames[:, t].contiguous()) for t in range(T)]
             self.check_status(wait=True)
-        out = torch.stack(outs, dim=1)
-        return out.cpu().numpy() if was_numpy else out
+        return self._deliver(torch.stack(outs, dim=1), was_numpy)

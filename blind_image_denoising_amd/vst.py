@@ -11,16 +11,15 @@ grey levels without the bias the algebraic inverse has.  Two kernels of csrc/vst
 `noise_level_function` leaves there: the fit never comes to the host.  DESIGN.md 7.11 has the formulas and what was measured.
 There is no CPU execution path.
 """
-from typing import Dict, Iterable
+from typing import Dict, Iterable, Optional
 
 import numpy as np
 import torch
 
 from . import _args as A
 from . import _native as N
-from .constants import DENOISER_STR
 from .metrics import image_metrics, summarise
-from .module_denoiser import DenoiserModule, float_form
+from .module_denoiser import DenoiserWrapper
 from .noise_level import NoiseLevelFunction, camera_noise, noise_level_function
 
 GAIN_MAX, OFFSET_MAX = 64.0, 65025.0
@@ -101,61 +100,39 @@ def unstabilise(stabilised_f32: torch.Tensor, noise_level, inverse: str = "exact
     return out
 
 
-class StabilisedDenoiserModule:
-    """A denoiser run between the variance-stabilising transform and its inverse: uint8 [B,H,W,C] -> uint8 [B,H,W,C] (float32,
-    not rounded, with cast_to_uint8=False).  `module`: a DenoiserModule, a SelfEnsembleDenoiserModule, or any callable that maps a
-    uint8 device tensor [N,H,W,C] to float32 of the same shape; its float32 form is what runs (module_denoiser.float_form).
+def parse_setting(stabilise) -> Optional[dict]:
+    """load_model's `stabilise`: None | False -> None; True -> the fit per frame; a (gain, offset) pair -> that pair.  Everything
+    is checked here, before anything is loaded."""
+    if stabilise is not None and not isinstance(stabilise, (bool, tuple, list)):
+        raise ValueError(f"stabilise must be None, a bool or a (gain, offset) pair, got {stabilise!r}")
+    if stabilise is None or stabilise is False:
+        return None
+    if stabilise is True:
+        return {}
+    _checked_noise_level(stabilise)
+    return {"noise_level": stabilise}
 
-    A call is: the argument checks and host-or-device input handling of DenoiserModule; with `noise_level=None` the fit
+
+class StabilisedDenoiserModule(DenoiserWrapper):
+    """A denoiser run between the variance-stabilising transform and its inverse: uint8 [B,H,W,C] -> uint8 [B,H,W,C] (float32,
+    not rounded, with cast_to_uint8=False).  `module`, argument checks, input handling, return types, empty batches and f16-range
+    status as every wrapper (DenoiserWrapper).
+
+    A call is: with `noise_level=None` the fit
     noise_level_function(image, min_cells), per image of the batch given, on the device (needs H, W >= 3); stabilise_u8; the float
     module; unstabilise(inverse).  A fixed `noise_level` (a NoiseLevelFunction or a (gain, offset) pair, as stabilise_u8 takes it)
     of shape [B,C] must match the batch, else ValueError.  `last_noise_level` holds the fit of the last call (the
-    NoiseLevelFunction, device tensors), or the fixed pair as it was given.
-
-    The f16-range status of the inner calls is kept where the wrapped module keeps its own: `check_status` is the wrapped
-    module's, and a host-array call that hits the range switches the model to the exact-fp32 kernels and repeats itself, as a
-    DenoiserModule call does.  With gain 0 the forward map is the identity and the inverse x = rc (w / s) = w up to two float32
-    roundings: the wrapper then returns what the module returns to within those."""
+    NoiseLevelFunction, device tensors), or the fixed pair as it was given.  With gain 0 the forward map is the identity and the
+    inverse x = rc (w / s) = w up to two float32 roundings: the wrapper then returns what the module returns to within those."""
+    SETTINGS = ("noise_level", "inverse", "min_cells")
 
     def __init__(self, module, noise_level=None, inverse: str = "exact", cast_to_uint8: bool = True, min_cells: int = 64):
         if isinstance(module, StabilisedDenoiserModule):
             raise ValueError("module is already stabilised")
-        self._float = float_form(module)                         # ValueError for what is not callable
-        self._module, self._inverse, self._cast_to_uint8 = module, A.one_of(inverse, "inverse", INVERSES), bool(cast_to_uint8)
-        self._min_cells = A.int_in(min_cells, "min_cells", 1)
+        self._wrap(module, cast_to_uint8)
+        self._inverse, self._min_cells = A.one_of(inverse, "inverse", INVERSES), A.int_in(min_cells, "min_cells", 1)
         self._noise_level = None if noise_level is None else _checked_noise_level(noise_level)
-        base = module if isinstance(module, DenoiserModule) else getattr(module, "_module", None)
-        self._base = base if isinstance(base, DenoiserModule) else None      # whose argument checks and empty output a call uses
-        self.name = getattr(module, "name", DENOISER_STR)
         self.last_noise_level = None
-
-    @property
-    def model_hydra(self):
-        return getattr(self._module, "model_hydra", None)
-
-    @property
-    def noise_level(self):
-        return self._noise_level
-
-    @property
-    def inverse(self) -> str:
-        return self._inverse
-
-    @property
-    def min_cells(self) -> int:
-        return self._min_cells
-
-    def check_status(self, wait: bool = True) -> bool:
-        return self._module.check_status(wait) if hasattr(self._module, "check_status") else True
-
-    def float_form(self) -> "StabilisedDenoiserModule":
-        """the whole pipeline -- transform, module, inverse -- with the same settings, not rounded"""
-        return StabilisedDenoiserModule(self._module, self._noise_level, self._inverse, cast_to_uint8=False, min_cells=self._min_cells)
-
-    def _checked_input(self, image):
-        if self._base is not None:
-            return self._base._checked_input(image)
-        return A.host_or_device(image, "image", (torch.uint8,), min_hw=0, allow_empty=True)      # no base module: any callable
 
     def __call__(self, image):
         image, was_numpy = self._checked_input(image)
@@ -164,28 +141,17 @@ class StabilisedDenoiserModule:
             for value, what in zip(self._noise_level, ("gain", "offset")):
                 A.broadcasts_to(value.shape, B, C, what)
         if B == 0:
-            if self._base is not None:
-                return self._base._empty_output(image, was_numpy)
-            return image.numpy() if was_numpy else image
-        hydra = self.model_hydra
-        if hydra is not None:
-            hydra._require_gpu()
-            image = image.to(hydra.device)
-        else:
-            image = A.to_device(image, was_numpy, None, "image", _FEATURE)
-        image = image.contiguous()
+            return self._empty_output(image, was_numpy)
+        image = self._place(image, was_numpy, "image", _FEATURE)
         if self._noise_level is None:
             level = noise_level_function(image, self._min_cells)
-            self.last_noise_level = level
         else:
-            level = self.last_noise_level = self._noise_level
-        result = self._float(stabilise_u8(image, level))
-        if was_numpy and not self.check_status(wait=True):
-            # host arrays are handed back and an activation left the f16 range: the model now runs the exact-fp32 kernels
-            # (check_status switched it); repeat the call
+            level = self._noise_level
+        self.last_noise_level = level
+        result = self._run(stabilise_u8(image, level))
+        if self._repeat_in_fp32(was_numpy):
             return self(image.cpu().numpy())
-        out = unstabilise(A.module_result(result, torch.float32, image.shape).to(image.device), level, self._inverse, self._cast_to_uint8)
-        return out.cpu().numpy() if was_numpy else out
+        return self._deliver(unstabilise(result.to(image.device), level, self._inverse, self._cast_to_uint8), was_numpy)
 
 
 # ---- evaluation on synthetic camera noise --------------------------------------------------------

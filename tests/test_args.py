@@ -187,6 +187,106 @@ def test_float_form_of_anything_else():
         float_form(3, "model")
 
 
+# ---- the protocol of DenoiserWrapper, held by every wrapper class --------------------------------------------------------------
+
+_DENOISE = lambda u8: u8.float()
+_WRAPPER_CASES = {                                                # class, settings away from the defaults, what it is built on
+    "self_ensemble": (bf.SelfEnsembleDenoiserModule, {"transforms": (1, 5)}, "module"),    # takes a DenoiserModule alone
+    "tiled": (bf.TiledDenoiserModule, {"tile": 32, "overlap": 12, "margin": 3, "tile_batch": 4}, _DENOISE),
+    "pixel_shuffle": (bf.PixelShuffleDenoiserModule,
+                      {"stride": "auto", "max_stride": 3, "threshold": 0.7, "refine": 4, "replace": 0.2, "seed": 9}, _DENOISE),
+    "stabilised": (bf.StabilisedDenoiserModule, {"noise_level": ([0.1, 0.2, 0.3], 4.0), "inverse": "algebraic", "min_cells": 32}, _DENOISE),
+    "burst": (bf.BurstDenoiserModule, {"reference": 1, "levels": 2, "search": 3, "sigma": 12.5, "k": (1.0, 2.5)}, _DENOISE),
+    "video": (bf.VideoDenoiserModule, {"n_max": 5, "levels": 2, "search": 3, "sigma": 12.5, "k": (1.0, 2.5)}, _DENOISE),
+    "nlm": (bf.NlmDenoiserModule, {"sigma": 7.0, "patch": 2, "search": 5, "strength": 0.4}, None),      # wraps nothing
+}
+
+
+def _same_setting(a, b) -> bool:
+    if isinstance(a, (tuple, list)):
+        return type(a) is type(b) and len(a) == len(b) and all(_same_setting(x, y) for x, y in zip(a, b))
+    return type(a) is type(b) and bool(np.all(np.asarray(a) == np.asarray(b)))
+
+
+@pytest.mark.parametrize("case", sorted(_WRAPPER_CASES))
+def test_every_wrapper_holds_the_base_protocol(case, module, monkeypatch):
+    cls, settings, wrapped = _WRAPPER_CASES[case]
+    wrapped = module if wrapped == "module" else wrapped
+    w = cls(**settings) if cls is bf.NlmDenoiserModule else cls(wrapped, **settings)
+    assert isinstance(w, bf.DenoiserWrapper) and tuple(cls.SETTINGS) == tuple(settings) and w._cast_to_uint8 is True
+    assert w._module is wrapped and w._base is (module if wrapped is module else None)
+    f = w.float_form()
+    assert type(f) is cls and f is not w and f._cast_to_uint8 is False and f._module is w._module and f._base is w._base
+    assert hasattr(f, "_record") == hasattr(w, "_record") and getattr(f, "_record", None) is getattr(w, "_record", None)
+    assert case in ("self_ensemble", "stabilised") or isinstance(w._record, dict)             # the two that keep no record
+    for name in cls.SETTINGS:
+        assert _same_setting(getattr(f, name), getattr(w, name)) and getattr(w, name) is getattr(w, "_" + name)
+        with pytest.raises(AttributeError):
+            setattr(w, name, getattr(w, name))
+    for name, value in settings.items():
+        if case != "stabilised" or name != "noise_level":
+            assert getattr(w, name) == value
+    if case == "stabilised":
+        assert w.noise_level[0].tolist() == [0.1, 0.2, 0.3] and float(w.noise_level[1]) == 4.0
+    assert w.check_status() is True and f.check_status(wait=False) is True
+    assert w.model_hydra is (module.model_hydra if wrapped is module else None)
+    # a well-formed host tensor: there is nowhere to run it.  (Over a model that lives on the host the model says so itself)
+    shape = (1, 2, 16, 16, 3) if case == "burst" else (1, 16, 16, 3)
+    with pytest.raises(RuntimeError, match="no CPU execution path") as e:
+        w(torch.zeros(shape, dtype=torch.uint8))
+    assert wrapped is module or "must live on the GPU" in str(e.value)
+    # an empty batch comes back before anything is placed or launched
+    def touched(*args, **kwargs):
+        raise AssertionError("an empty batch reached the GPU")
+    monkeypatch.setattr(bf._native, "call", touched)
+    monkeypatch.setattr(A, "to_device", touched)
+    monkeypatch.setattr(type(module.model_hydra), "_require_gpu", touched)
+    for given in (np.zeros((0,) + shape[1:], np.uint8), torch.zeros((0,) + shape[1:], dtype=torch.uint8)):
+        for m in (w, f):
+            out = m(given)
+            assert type(out) is type(given) and tuple(out.shape) == (0, 16, 16, 3) and "uint8" in str(out.dtype)
+
+
+# ---- load_model's options: each is parsed before anything is loaded ----------------------------------------------------------
+
+@pytest.mark.parametrize("option, parse, unknown_key, wrong_type, bad_value, good", [
+    ("self_ensemble", bf.self_ensemble.parse_setting, None, 3, [8], "flips"),               # not a dict option: no keys
+    ("tiled", bf.tiling.parse_setting, {"tiles": 64}, "yes", {"tile": 0}, {"tile": 64}),
+    ("pixel_shuffle", bf.pixel_shuffle.parse_setting, {"strides": 2}, 2.5, {"stride": 12}, 2),
+    ("stabilise", bf.vst.parse_setting, None, "yes", (-1.0, 0.0), (0.5, 4.0)),               # not a dict option: no keys
+    ("burst", bf.burst.parse_setting, {"n_max": 2}, "yes", {"levels": 9}, {"levels": 2}),
+    ("video", bf.video_settings, {"reference": 0}, 3, {"n_max": 65}, {"n_max": 4}),
+    ("nlm", bf.nlm_settings, {"radius": 2}, True, {"patch": 4}, {"patch": 2}),
+])
+def test_every_load_model_option_is_parsed_before_anything_is_loaded(option, parse, unknown_key, wrong_type, bad_value, good):
+    path = "nlm" if option == "nlm" else "no such model"         # reaching the loader says "does not exist"
+    for bad in (unknown_key, wrong_type, bad_value):
+        if bad is None:
+            continue
+        with pytest.raises(ValueError) as e:
+            parse(bad)
+        assert "does not exist" not in str(e.value)
+        with pytest.raises(ValueError) as e:
+            bf.load_model(path, **{option: bad})
+        assert "does not exist" not in str(e.value)
+    if unknown_key is not None:
+        with pytest.raises(ValueError, match=f"{option} may set"):
+            parse(unknown_key)
+    if option == "nlm":                                           # no wrapper but the model itself: None is its defaults
+        assert parse(None) == {} and parse(good) == good
+        return
+    assert parse(None) is None and parse(good) is not None
+    if option == "self_ensemble":                                 # the one option that is no switch: False names no transforms
+        with pytest.raises(ValueError, match="transforms"):
+            parse(False)
+    else:
+        assert parse(False) is None
+    with pytest.raises(ValueError, match="does not exist"):       # a good value, and values that ask for no wrapper, reach the loader
+        bf.load_model(path, **{option: good})
+    with pytest.raises(ValueError, match="does not exist"):
+        bf.load_model(path, **{option: None})
+
+
 # ---- the import graph --------------------------------------------------------------------------------------------------------
 
 def test_vst_imports_on_its_own_and_no_feature_module_imports_inside_a_function_to_dodge_a_cycle():

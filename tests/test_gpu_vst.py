@@ -371,3 +371,28 @@ def test_trained_network_on_camera_noise_is_recorded():
             assert out.dtype == np.uint8 and out.shape == clean.shape
             print(f"    {what:<20} PSNR {K.psnr(clean, out):6.2f} dB   MAE {K.mae(clean, out):6.3f}")
         assert bool(torch.isfinite(fit.gain).all()) and bool(torch.isfinite(fit.offset).all())
+
+
+# ---- 10. a stack three deep: the outermost wrapper finds the model's own argument checks ---------------------------------------
+
+def test_a_three_deep_stack_checks_channels_and_empty_batches_as_its_model_does():
+    """Every wrapper finds the DenoiserModule at the bottom through the whole chain (DenoiserWrapper._base): a wrong channel count
+    is the model's ValueError, raised by the outermost wrapper's input check before anything is uploaded, and an empty batch
+    comes back as the model's empty output (its out_channels), not as the input."""
+    hydra = bf.model_builder(O.canonical_config(no_layers=6)["model"], device="cuda").hydra
+    base = bf.DenoiserModule(hydra)
+    stack = bf.StabilisedDenoiserModule(bf.PixelShuffleDenoiserModule(bf.TiledDenoiserModule(base)))
+    assert stack._base is base and stack._module._base is base and stack._module._module._base is base
+    wrong = np.zeros((1, 16, 16, 4), np.uint8)
+    with pytest.raises(ValueError) as of_the_model:
+        base(wrong)
+    assert "3..3 channels" in str(of_the_model.value)
+    for given in (wrong, _dev(wrong), wrong[:0], _dev(wrong[:0])):
+        with pytest.raises(ValueError) as e:
+            stack(given)
+        assert str(e.value).replace("(0, ", "(1, ") == str(of_the_model.value)
+    assert stack.last_noise_level is None and stack._module.last_stride is None         # nothing ran
+    for given in (np.zeros((0, 16, 16, 3), np.uint8), torch.zeros((0, 16, 16, 3), dtype=torch.uint8)):
+        out = stack(given)
+        assert type(out) is type(given) and out is not given and "uint8" in str(out.dtype)
+        assert tuple(out.shape) == (0, 16, 16, hydra.desc.out_channels)
