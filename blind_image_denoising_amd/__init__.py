@@ -56,6 +56,9 @@ from .video import parse_setting as video_settings
 from . import nlm as _nlm
 from .nlm import NlmDenoiserModule, nlm, nlm_params, nlm_table, nlm_tune
 from .nlm import parse_setting as nlm_settings
+from . import bm3d as _bm3d
+from .bm3d import Bm3dDenoiserModule, bm3d, bm3d_params, bm3d_step
+from .bm3d import parse_setting as bm3d_settings
 from . import restore as _restore
 from .restore import (RestoreConstraint, RestoreResult, mask_constraint, block_constraint, restore_init, restore_direction,
                       restore_step, restore_finish, restore, inpaint, super_resolve, bayer_mask)
@@ -115,7 +118,7 @@ _WRAPPERS = (("self_ensemble", _self_ensemble.parse_setting, SelfEnsembleDenoise
 
 
 def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None, tiled=None, pixel_shuffle=None, burst=None,
-               nlm=None, video=None):
+               nlm=None, video=None, bm3d=None):
     """bfcnn/__init__.py:81-97: a registry name, a model directory (pipeline.json + weights.npz written by
     `save_model`), or a `.keras` archive of a trained unet_laplacian hydra / the directory holding `model_hydra.keras`
     (the layout of the reference's bfcnn/pretrained/<name>/).  Returns a callable uint8 [B,H,W,C] -> uint8 [B,H,W,C]: a
@@ -135,17 +138,22 @@ def load_model(model_path: str, device=None, self_ensemble=None, stabilise=None,
 
     `burst` and `video` both wrap outermost: both together are a ValueError.  The name "nlm" is no network: it returns a
     NlmDenoiserModule (non-local means, nlm.py; any channel count 1..4, no weights) under the same wrappers; `nlm` = None or a
-    dict of its settings (sigma, patch, search, strength), a ValueError with any other `model_path`.  Every option is checked
-    before anything is loaded."""
+    dict of its settings (sigma, patch, search, strength), a ValueError with any other `model_path`.  The name "bm3d" likewise
+    returns a Bm3dDenoiserModule (block matching and collaborative filtering, bm3d.py); `bm3d` = None or a dict of its settings
+    (sigma, search, step, threshold, wiener).  Every option is checked before anything is loaded."""
     options = {"self_ensemble": self_ensemble, "tiled": tiled, "pixel_shuffle": pixel_shuffle, "stabilise": stabilise, "burst": burst,
                "video": video}
-    if nlm is not None and model_path != _nlm.MODEL_NAME:
-        raise ValueError(f"nlm sets the non-local means of load_model({_nlm.MODEL_NAME!r}), got it with model_path {model_path!r}")
-    filter_settings = nlm_settings(nlm) if model_path == _nlm.MODEL_NAME else None
+    # the filters that are no network: name -> (the option that sets it, its value, its parse_setting, its module)
+    filters = {_nlm.MODEL_NAME: ("nlm", nlm, nlm_settings, NlmDenoiserModule),
+               _bm3d.MODEL_NAME: ("bm3d", bm3d, bm3d_settings, Bm3dDenoiserModule)}
+    for name, (keyword, value, _, _) in filters.items():
+        if value is not None and model_path != name:
+            raise ValueError(f"{keyword} sets the filter of load_model({name!r}), got it with model_path {model_path!r}")
+    filter_settings = filters[model_path][2](filters[model_path][1]) if model_path in filters else None
     settings = {keyword: parse(options[keyword]) for keyword, parse, _ in _WRAPPERS}
     if settings["burst"] is not None and settings["video"] is not None:
         raise ValueError("burst and video both wrap outermost: set one of them")
-    module = _load_module(model_path, device) if filter_settings is None else NlmDenoiserModule(**filter_settings)
+    module = _load_module(model_path, device) if filter_settings is None else filters[model_path][3](**filter_settings)
     for keyword, _, wrapper in _WRAPPERS:
         if settings[keyword] is not None:
             module = wrapper(module, **settings[keyword])

@@ -197,6 +197,8 @@ SIGNATURES = {
     "bf_op_burst_merge": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "bf_op_video_update": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "bf_op_nlm": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "bf_op_bm3d_step": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "bf_op_bm3d_finish": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P]),
     "bf_op_restore_scratch_bytes": (_I64, [_I, _I, _I, _I]),
     "bf_op_restore_init": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _D, C.c_uint64, _P, _P]),
     "bf_op_restore_direction": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I64, _P, _P]),

@@ -823,6 +823,43 @@ int bf_op_video_update(const uint8_t* x, const uint16_t* acc_in, const uint16_t*
 int bf_op_nlm(const uint8_t* images, const int64_t* params, const int32_t* table, int B, int H, int W, int C, int patch, int search,
               void* out, int cast_to_uint8, int32_t* weights_or_null, void* stream);
 
+/* ---- BM3D: block matching and collaborative filtering (Dabov, Foi, Katkovnik, Egiazarian 2007; blind_image_denoising_amd/bm3d.py
+ * is the host side; csrc/bm3d.hip) ----
+ * noisy, guide = uint8 [B,H,W,C], C in 1..4, H, W >= 8, B H W C < 2^31; `search` = r in 1..12, `step` in 1..8.  Blocks are 8 x 8, a
+ * group holds at most 16.  Hn = the Sylvester Hadamard matrix, H2n = [[Hn, Hn], [Hn, -Hn]].  Per C a forward matrix A with squared
+ * row norms n2 and a back matrix Bk, Bk A = s I:  C = 1: [1], s = 1;  C = 2: A = Bk = H2, n2 = 2, s = 2;  C = 4: A = Bk = H4, n2 = 4,
+ * s = 4;  C = 3: A = [1,1,1], [1,0,-1], [1,-2,1], n2 = 3, 2, 6, Bk = [2,3,1], [2,0,-2], [2,-3,1], s = 6.
+ * params = int64 [B,4] = (tau1, thr1, tau2, v1) per image, each >= 0 (negative values are taken as 0; bm3d.bm3d_params makes them
+ * from a noise level).  `wiener` == 0 reads tau = tau1 and thr1, else tau = tau2 and v1.
+ * Reference blocks: top-left corners 0, step, 2 step, ... <= n - 8 and n - 8 along each axis.  For each, the candidates are the
+ * blocks (cy, cx) with max(0, y - r) <= cy <= min(H - 8, y + r) and the same in x (no padding):
+ *   D = the squared difference of the guide's blocks over 64 pixels and C channels (< 2^24); a candidate counts if D <= tau, the
+ *   reference itself always; key = (D << 10) | ((dy + r)(2 r + 1) + dx + r), the reference's own -1; the group is the first K by
+ *   ascending key, K = the largest power of two <= min(count, 16).
+ *   t = H8 block H8 of the noisy blocks, then HK along the group, then A along the channels (|t| <= 255 * 64 * 16 * 4 < 2^20); with
+ *   `wiener` tb = the same of the guide's blocks.
+ *   wiener == 0:  t stays where t t > (thr1 K) n2[c], else 0; w = max(4096 / max(number kept, 1), 1).
+ *   wiener != 0:  S = tb tb, g = (S << 12) / max(S + (v1 K) n2[c], 1) (<= 4096; S << 12 <= 2^52), t = (t g + 2048) >> 12
+ *                 (arithmetic shift); w = min(max(2^36 / max(sum of g g, 1), 1), 2^14)  (sum of g g <= 2^36).
+ *   back: Bk along the channels, HK along the group, H8 . H8 per block, times 16 / K: the scale is 1024 s.
+ *   acc [B,H,W,C+1] int64: for every pixel of the K blocks num[pixel, c] += w value, den[pixel] += w (den is the last entry).
+ * Bounds.  |t| never grows in the shrinkage, and a back transform of any subset of 2^m coefficients is at most 2^(m/2) times their
+ * root sum of squares, so with rowabs(A) = (3, 2, 4) and a row of |Bk| = (2, 3, 1) (C = 3; 4 x 4 for C = 4) every back value is
+ * below 2^15 * 255 * 16 < 2^27 and the kernel's transform is 32-bit.  One contribution w value is below 2^41.  A pixel lies in 64
+ * blocks, each a member of at most (2 r + 1)^2 groups: at step 1 and r = 12 that is 40 000 < 2^16 contributions, |num| < 2^57,
+ * den < 2^30, and d = den 1024 s < 2^43 below.
+ * bf_op_bm3d_step zeroes acc on the stream (hipMemsetAsync) and launches; a tile of reference blocks is summed in LDS first.  Integer sums: the result
+ * does not depend on the order of the atomic adds.  No allocation, no synchronisation: graph-capturable.
+ * bf_op_bm3d_finish: d = den 1024 s; out [B,H,W,C] = uint8 min((2 max(num, 0) + d) / (2 d), 255) (integer division), or with
+ * cast_to_uint8 == 0 (float) ((double) num / (double) d), one correctly rounded division and one cast, not clipped;
+ * weights_or_null = int64 [B,H,W] = den (>= 1 after a step: every pixel lies in a reference block).
+ * BF_EINVAL for NULL (but weights_or_null), a bad shape or setting, a misaligned pointer (8 bytes for params, acc and weights, 4
+ * for a float out), or when acc is one of the other buffers. */
+int bf_op_bm3d_step(const uint8_t* noisy, const uint8_t* guide, const int64_t* params, int B, int H, int W, int C, int search, int step,
+                    int wiener, int64_t* acc, void* stream);
+int bf_op_bm3d_finish(const int64_t* acc, int B, int H, int W, int C, void* out, int cast_to_uint8, int64_t* weights_or_null,
+                      void* stream);
+
 /* ---- restoration with the denoiser's implicit prior: the state update of Kadkhodaie & Simoncelli, "Stochastic solutions for linear
  * inverse problems using the prior implicit in a denoiser" (NeurIPS 2021), Algorithm 2, between two denoiser calls
  * (blind_image_denoising_amd/restore.py is the host side; csrc/restore.hip) ----

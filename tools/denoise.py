@@ -2,8 +2,8 @@
 
     python tools/denoise.py unet_laplacian_v5.6 photos/ denoised/ --tile 256 --stabilise
 
-MODEL is a registry name (blind_image_denoising_amd.models), a model directory or `nlm` (non-local means: no network); IN_DIR is walked for image files, and every
-result is written to the same relative path below OUT_DIR (as PNG where the source format is lossy or has no writer).  Every frame
+MODEL is a registry name (blind_image_denoising_amd.models), a model directory, `nlm` or `bm3d` (non-local means, BM3D: no
+network); IN_DIR is walked for image files, and every result is written to the same relative path below OUT_DIR (as PNG where the source format is lossy or has no writer).  Every frame
 is cut into overlapping tiles of --tile pixels, the model runs on batches of --tile-batch tiles of one shape, and the results are
 blended: --overlap and --margin default to what the model needs (its receptive radius where it has one).  --self-ensemble d4 |
 flips averages the model over flips and rotations of every tile; --stabilise fits camera noise (variance = gain x + offset) on

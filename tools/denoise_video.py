@@ -2,7 +2,7 @@
 
     python tools/denoise_video.py unet_laplacian_v5.6 frames/ denoised/ --n-max 8 --tile 256
 
-MODEL is a registry name (blind_image_denoising_amd.models), a model directory, "nlm" (non-local means, no weights) or "none" (the
+MODEL is a registry name (blind_image_denoising_amd.models), a model directory, "nlm" or "bm3d" (non-local means, BM3D: no weights) or "none" (the
 temporal filter alone).  The image files directly in IN_DIR are the frames, in name order; all of them must have the same size.
 Every frame is filtered recursively along the motion against what the stream has accumulated (up to --n-max frames per pixel),
 then denoised, tile by tile with --tile; the result is written to OUT_DIR under the frame's name as PNG.  --sigma fixes the noise

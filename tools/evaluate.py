@@ -4,9 +4,9 @@ table, measured on the GPU by blind_image_denoising_amd.evaluate.  It reads only
 
     python tools/evaluate.py unet_laplacian_v5.6 frames/*.png --noise-std 10 15 20 25 30 --json report.json
 
-MODEL is a registry name (blind_image_denoising_amd.models), a model directory or `nlm` (non-local means: the classical baseline
-to put next to a network's numbers); IMAGES are files or directories.  Every image is
-its own batch, so frames of different sizes can be mixed; --size H W resizes them first."""
+MODEL is a registry name (blind_image_denoising_amd.models), a model directory, `nlm` or `bm3d` (non-local means, BM3D: the
+classical baselines to put next to a network's numbers); IMAGES are files or directories.  Every image is its own batch,
+so frames of different sizes can be mixed; --size H W resizes them first."""
 import argparse
 import json
 import os
