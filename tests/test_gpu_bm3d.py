@@ -13,8 +13,9 @@ import bm3d_reference as R
 import burst_reference
 import nlm_reference
 import tiling_reference
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 # (H, W, C, search, step) at B = 2.  8 x 8 is one block (K = 1), 8 x 13 has the extra position n - 8, 16 x 16 has few candidates
 # (small K), 37 x 45 is odd, 70 x 83 is larger than any search region, so that windows and groups lie anywhere in the frame
@@ -23,10 +24,6 @@ CASES = [(8, 8, 1, 12, 4), (8, 13, 3, 3, 4), (16, 16, 3, 12, 4), (16, 16, 4, 2, 
 _ids = {"ids": lambda c: "-".join(map(str, c))}
 SIGMAS = [9.0, 14.0]                                                 # different parameters per image, around the scenes' sigma of 12
 SMALL_GROUPS = (300.0, 48.0)                                         # match thresholds under which few candidates count
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _same(got, ref):

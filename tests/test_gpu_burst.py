@@ -9,8 +9,9 @@ import torch
 import blind_image_denoising_amd as bf
 from oracle import bfcnn_oracle as O
 import burst_reference as R
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 # (H, W, C, T, reference, levels, search) at B = 2.  5 x 7 is smaller than a tile, 16 x 16 is one tile, 37 x 45 is odd at every level
 # and has cut edge tiles, 64 x 96 has six tiles in a row (two workgroups of four waves, the second half empty)
@@ -19,10 +20,6 @@ CASES = [(5, 7, 1, 1, 0, 1, 1), (5, 7, 3, 2, 1, 4, 4), (5, 7, 3, 5, 0, 3, 7),
          (37, 45, 3, 5, 4, 3, 4), (37, 45, 1, 2, 0, 4, 7), (37, 45, 3, 2, 1, 1, 1), (37, 45, 1, 5, 0, 3, 7),
          (64, 96, 3, 5, 0, 3, 4), (64, 96, 1, 2, 1, 4, 1), (64, 96, 3, 2, 0, 1, 7), (64, 96, 3, 5, 4, 4, 4)]
 _ids = {"ids": lambda c: "-".join(map(str, c))}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _same(got, ref):

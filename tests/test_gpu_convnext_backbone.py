@@ -14,9 +14,10 @@ from blind_image_denoising_amd import unet_laplacian as UL
 from oracle import bfcnn_oracle as O
 from oracle import resnet_generic_torch as RT
 import convnext_torch as CT
-from helpers import dev, host, assert_close
+from helpers import host, assert_close
+from guarded import dev as dev_raw, dev_f32 as dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 # bf_op_dwconv_ln at k = 7 walks strips of 8 rows, or of 32 rows once 32-row strips give at least 512 workgroups
 STRIP_SMALL, STRIP_LARGE = 8, 32
@@ -160,7 +161,7 @@ def _train_parity(bb, shape=(2, 32, 32), seed=5):
               for key in range(m.no_layers)}
         ds[0][:] = 0.0                                                     # one block off for sure, the rest as drawn
         ds[m.no_layers - 1][:] = 1.0 / np.float32(1 - spec.dropout_rate)
-        fns.train_step_single_gpu.drop_scale = {k: torch.from_numpy(v).cuda() for k, v in ds.items()}
+        fns.train_step_single_gpu.drop_scale = {k: dev_raw(v) for k, v in ds.items()}
     total, model_loss, [dl], pred, grads = fns.train_step_single_gpu(torch.from_numpy(gt), torch.from_numpy(x))
     r_total, r_reg, r_dl, r_pred, r_grads, r_state = CT.train_step(spec, O.LossSpec.from_config(LOSS), params, state,
                                                                    gt.astype(np.float64), x.astype(np.float64), ds)

@@ -7,12 +7,9 @@ import torch
 
 from blind_image_denoising_amd import _native as N
 from oracle import resnet_generic_oracle as G
+from guarded import dev_f32 as _d, guard_bands
 
-pytestmark = pytest.mark.gpu
-
-
-def _d(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 
 @pytest.mark.parametrize("C,m", [(32, 4), (3, 2), (64, 1)])

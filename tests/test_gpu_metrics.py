@@ -19,8 +19,9 @@ from blind_image_denoising_amd import _native as N
 from blind_image_denoising_amd import metrics as M
 from oracle import bfcnn_oracle as O
 import unet_v56 as V
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 SSIM_BOUND = 4 * 6.9e-13            # 4 x the largest |ssim - oracle| measured over test_ssim_matches_the_oracle's cases
 F32_SUM_REL_BOUND = 4 * 3.8e-16     # 4 x the largest relative deviation measured over test_float32_sums_match_numpy's cases
@@ -50,7 +51,7 @@ def test_uint8_sums_are_exact(shape):
     rng = np.random.default_rng(sum(shape))
     a, b = rng.integers(0, 256, shape, dtype=np.uint8), rng.integers(0, 256, shape, dtype=np.uint8)
     a[0, 0, 0, 0], b[0, 0, 0, 0], a[-1, -1, -1, -1], b[-1, -1, -1, -1] = 255, 0, 0, 255        # the corners count, once
-    sums = bf.image_metric_sums(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()).cpu().numpy()
+    sums = bf.image_metric_sums(_dev(a), _dev(b)).cpu().numpy()
     d = a.astype(np.int64) - b.astype(np.int64)
     assert sums.dtype == np.float64 and sums.shape == (shape[0], 4)
     assert np.array_equal(sums[:, 0], (d * d).sum(axis=(1, 2, 3)).astype(np.float64))
@@ -65,7 +66,7 @@ def test_uint8_sums_are_exact(shape):
 @pytest.mark.parametrize("dtype", [np.uint8, np.float32])
 def test_identical_images(dtype):
     a = np.random.default_rng(3).integers(0, 256, (3, 40, 70, 3)).astype(dtype)
-    t = torch.from_numpy(a).cuda()
+    t = _dev(a)
     m = bf.image_metrics(t, t.clone())
     assert all(v.is_cuda and v.dtype == torch.float64 and v.shape == (3,) for v in m)
     assert (m.mse == 0).all() and (m.mae == 0).all() and torch.isinf(m.psnr).all() and (m.psnr > 0).all()
@@ -103,7 +104,7 @@ def test_ssim_matches_the_oracle():
                     r = _oracle_ssim(x, y, filter_size)
                 else:
                     r = ref
-                got = bf.ssim(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda(), filter_size=filter_size).cpu().numpy()
+                got = bf.ssim(_dev(x), _dev(y), filter_size=filter_size).cpu().numpy()
                 dev = float(np.abs(got - r).max())
                 worst = max(worst, dev)
                 print(f"ssim {name} {filter_size}x{filter_size} {np.dtype(dtype).name}: {got[0]:.6f}, max |dev| = {dev:.3e}")
@@ -117,7 +118,7 @@ def test_float32_sums_match_numpy():
     for shape in [(1, 11, 11, 3), (2, 37, 53, 3), (3, 256, 256, 3), (1, 375, 1242, 3), (2, 50, 70, 1)]:
         a = rng.uniform(0, 255, shape).astype(np.float32)
         b = (a + rng.normal(0, 10, shape)).astype(np.float32)
-        sums = bf.image_metric_sums(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()).cpu().numpy()
+        sums = bf.image_metric_sums(_dev(a), _dev(b)).cpu().numpy()
         d = a.astype(np.float64) - b.astype(np.float64)
         ref = np.stack([(d * d).sum(axis=(1, 2, 3)), np.abs(d).sum(axis=(1, 2, 3))], axis=1)
         dev = float((np.abs(sums[:, :2] - ref) / ref).max())
@@ -137,8 +138,8 @@ def test_agrees_with_the_training_loss_ssim():
     m.set_weights(params, state)
     fns = bf.build_train_functions(m, bf.loss_function_builder(cfg["loss"]))
     clean, noisy = O.synthetic_batch(3, 24, 40, seed=11)
-    gt = torch.from_numpy(clean.astype(np.float32)).cuda()
-    _, _, dl, pred, _ = fns.train_step_single_gpu(gt, torch.from_numpy(noisy.astype(np.float32)).cuda(), (1.0,), 0.0, None)
+    gt = _dev(clean.astype(np.float32))
+    _, _, dl, pred, _ = fns.train_step_single_gpu(gt, _dev(noisy.astype(np.float32)), (1.0,), 0.0, None)
     loss = float(dl[0]["ssim_loss"].item())
     got = 1.0 - float(bf.ssim(gt, pred.contiguous(), filter_size=7).mean())
     bound = SSIM_BOUND + TRAIN_SSIM_REL_BOUND * max(abs(loss), 1e-3)
@@ -148,7 +149,7 @@ def test_agrees_with_the_training_loss_ssim():
 
 def test_two_calls_are_bitwise_equal():
     clean = np.concatenate([_lena(256, 256)] * 5)
-    a, b = torch.from_numpy(clean).cuda(), torch.from_numpy(_noisy(clean, 20.0, 7)).cuda()
+    a, b = _dev(clean), _dev(_noisy(clean, 20.0, 7))
     for x, y in ((a, b), (a.float(), b.float())):
         first = bf.image_metric_sums(x, y).cpu().numpy()
         for _ in range(3):
@@ -196,7 +197,7 @@ def test_evaluate_reports_what_the_arrays_say():
     c0, _ = O.synthetic_batch(3, 48, 64, seed=1)
     c1, _ = O.synthetic_batch(2, 33, 80, seed=2)                                 # two shapes in one call
     levels = (10, 25)
-    report = bf.evaluate(rec, [c0, torch.from_numpy(c1).cuda()], noise_std=levels, seed=5)
+    report = bf.evaluate(rec, [c0, _dev(c1)], noise_std=levels, seed=5)
     assert [r["noise_std"] for r in report] == [10.0, 25.0] and len(rec.noisy) == 4
     for li, r in enumerate(report):
         parts = [_reference_level(c, rec.noisy[2 * li + bi], rec.denoised[2 * li + bi]) for bi, c in enumerate((c0, c1))]

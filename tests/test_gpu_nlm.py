@@ -12,8 +12,9 @@ import burst_reference
 import nlm_reference as R
 import risk_reference
 import tiling_reference
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 # (H, W, C, patch, search) at B = 2.  3 x 5 is smaller than a patch and than the search window, 16 x 16 lies inside one 32 x 32
 # tile, 37 x 45 is odd with cut edge tiles, 70 x 83 has three tiles each way, so that a search window of 10 crosses tile borders
@@ -23,10 +24,6 @@ CASES = [(3, 5, 1, 1, 1), (3, 5, 3, 3, 10), (3, 5, 4, 2, 3),
          (70, 83, 3, 1, 10), (70, 83, 1, 2, 10), (70, 83, 4, 3, 3), (70, 83, 3, 3, 10)]
 _ids = {"ids": lambda c: "-".join(map(str, c))}
 SIGMAS, STRENGTHS = [9.0, 14.0], np.array([0.55, 0.75])             # different parameters per image, around the scenes' sigma of 12
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _same(got, ref):

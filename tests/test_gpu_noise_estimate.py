@@ -19,15 +19,12 @@ import blind_image_denoising_amd as bf
 from blind_image_denoising_amd import _native as N
 from oracle import bfcnn_oracle as O
 import noise_reference as R
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 SHAPES = [(1, 3, 3, 1), (2, 4, 5, 3), (1, 37, 53, 3), (3, 64, 257, 4), (2, 70, 66, 3), (1, 33, 65, 1), (2, 9, 130, 2)]
 _ids = {"ids": lambda s: "x".join(map(str, s))}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _check_u8(images: np.ndarray, what: str):
@@ -192,7 +189,7 @@ def test_evaluate_blind_reports_what_the_arrays_say(method, slot):
     _, n0 = O.synthetic_batch(2, 64, 64, seed=1)
     _, n1 = O.synthetic_batch(1, 40, 72, sigma=40.0, seed=2)                      # two shapes in one call
     n0, n1 = n0.astype(np.uint8), n1.astype(np.uint8)
-    report = bf.evaluate_blind(rec, [n0, torch.from_numpy(n1).cuda()], method=method)
+    report = bf.evaluate_blind(rec, [n0, _dev(n1)], method=method)
     assert set(report) == {"method", "images", "batches", "aggregate"} and report["method"] == method and report["images"] == 3
     assert len(rec.noisy) == 2 and np.array_equal(rec.noisy[0], n0) and np.array_equal(rec.noisy[1], n1)
     refs = [_reference_rows(x, y, slot) for x, y in zip(rec.noisy, rec.denoised)]

@@ -29,18 +29,15 @@ from blind_image_denoising_amd import _native as N
 from oracle import bfcnn_oracle as O
 import noise_level_reference as L
 import risk_reference as RR
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 LEVEL_SHAPES = [(1, 3, 3, 1), (2, 4, 5, 3), (1, 37, 53, 3), (3, 64, 257, 4), (2, 70, 66, 3), (1, 33, 65, 1), (2, 9, 130, 2)]
 NOISE_SHAPES = [(1, 1, 1, 1), (2, 3, 5, 3), (1, 33, 65, 3), (2, 9, 130, 2), (3, 64, 257, 4)]
 SUMS_SHAPES = [(1, 1, 1, 1), (2, 3, 5, 3), (1, 37, 53, 3), (2, 9, 130, 2), (2, 65, 65, 1), (3, 64, 257, 4)]
 PROBES = [1, 3, 8]
 _ids = {"ids": lambda s: "x".join(map(str, s)) if isinstance(s, tuple) else f"K{s}"}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 # ---- 1. bf_noise_level -------------------------------------------------------------------------------------------------------

@@ -10,8 +10,9 @@ import torch
 import blind_image_denoising_amd as bf
 from oracle import bfcnn_oracle as O
 import pixel_shuffle_reference as R
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 # (B, H, W, C, S): H = S + 1, one position at s = 8; across a 32-row and a 64-column tile edge; four channels, three column tiles
 CORRELATION_CASES = [(1, 9, 9, 1, 8), (2, 40, 70, 3, 6), (1, 33, 130, 4, 4)]
@@ -20,10 +21,6 @@ SPLIT_CASES = [(1, 4, 4, 3, 2), (2, 7, 9, 3, 2), (1, 6, 200, 1, 3), (1, 65, 33, 
 # piece); three pieces of 170 columns with the repeat inside the last; stride 8 and four channels (the largest LDS segments)
 SPLIT_CASES += [(1, 4, 513, 3, 2), (2, 7, 1030, 1, 3), (1, 17, 530, 4, 8)]
 _ids = {"ids": lambda c: "-".join(map(str, c))}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _same(got, ref):

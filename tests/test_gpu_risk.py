@@ -26,17 +26,14 @@ from blind_image_denoising_amd import _native as N
 from oracle import bfcnn_oracle as O
 import risk_reference as R
 from test_gpu_inference import _check_f32
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 SHAPES = [(1, 1, 1, 1), (2, 3, 5, 3), (1, 37, 53, 3), (3, 64, 257, 4), (2, 9, 130, 2), (2, 65, 65, 1), (1, 33, 65, 3), (2, 40, 64, 3),
           (1, 32, 64, 3)]
 PROBES = [1, 3, 8]
 _ids = {"ids": lambda s: "x".join(map(str, s)) if isinstance(s, tuple) else f"K{s}"}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 # ---- 1. the probe stack ------------------------------------------------------------------------------------------------------
@@ -283,7 +280,7 @@ def test_evaluate_blind_risk_aggregates_batches_of_different_shapes():
     _, n0 = O.synthetic_batch(2, 64, 64, seed=1)
     _, n1 = O.synthetic_batch(1, 40, 72, sigma=40.0, seed=2)
     n1[0, :8, :8] = 255
-    report = bf.evaluate_blind_risk(module, [n0, torch.from_numpy(n1).cuda()], probes=2, amplitude=2, seed=2 ** 64 - 1)
+    report = bf.evaluate_blind_risk(module, [n0, _dev(n1)], probes=2, amplitude=2, seed=2 ** 64 - 1)
     assert set(report) == {"method", "probes", "amplitude", "images", "batches", "aggregate"}
     assert (report["method"], report["probes"], report["amplitude"], report["images"]) == ("mad", 2, 2, 3)
     keys = {"mse", "psnr", "sigma_in", "divergence", "clipped_fraction"}

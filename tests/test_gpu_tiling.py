@@ -16,18 +16,15 @@ from blind_image_denoising_amd import tiling as TL
 from oracle import bfcnn_oracle as O
 from oracle import unet_oracle as U
 import tiling_reference as R
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 # (B, H, W, C, T, O, M): one tile below T; three tiles over rows 23..26; the locality case, 21 tiles; one past a tile; R = 0, a
 # hard crop; no nominal overlap
 CASES = [(1, 1, 1, 3, 8, 4, 2), (2, 50, 70, 3, 32, 16, 5), (1, 64, 128, 3, 32, 16, 5), (1, 33, 65, 1, 32, 16, 0),
          (1, 7, 200, 3, 16, 8, 4), (3, 40, 40, 1, 16, 0, 0)]
 _ids = {"ids": lambda c: "-".join(map(str, c))}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _same(got, ref):
@@ -169,7 +166,7 @@ def test_end_to_end_is_the_hand_built_pipeline(name, shape):
         got = tiled(x)                                               # NumPy in, NumPy out
         assert isinstance(got, np.ndarray) and _same(got, ref)
         assert tiled.last_plan == bf.tile_plan(shape[1], shape[2], 32, 16, 4) and tiled.last_plan.tiles > 5
-        got_dev = tiled(torch.from_numpy(x).cuda())                  # device tensor in, device tensor out
+        got_dev = tiled(_dev(x))                                     # device tensor in, device tensor out
         assert isinstance(got_dev, torch.Tensor) and got_dev.is_cuda and _same(got_dev.cpu().numpy(), ref)
         assert tiled.check_status() is True
         assert tiled(x[:0]).shape == (0,) + shape[1:] and tiled(x[:0]).dtype == np.uint8
@@ -183,7 +180,7 @@ def test_batching_contract_calls(monkeypatch):
     real = hydra.infer_u8
     monkeypatch.setattr(hydra, "infer_u8", lambda image, cast=True: (seen.append((image.cpu().numpy(), cast)), real(image, cast))[1])
     x = np.random.default_rng(3).integers(0, 256, (1, 64, 128, 3), dtype=np.uint8)
-    tiled(torch.from_numpy(x).cuda())
+    tiled(_dev(x))
     tiles = R.split(x, 32, 16)
     n = tiles.shape[0]
     assert n == 21 and len(seen) == math.ceil(n / 5) and all(s[1] is False and s[0].shape == (5, 32, 32, 3) for s in seen)
@@ -191,7 +188,7 @@ def test_batching_contract_calls(monkeypatch):
         assert np.array_equal(s[0], tiles[5 * k:5 * k + 5])
     assert np.array_equal(seen[-1][0], tiles[n - 5:])
     del seen[:]
-    tiled(torch.from_numpy(x[:, :32, :48]).cuda())                   # N = 2 < tile_batch: one call on both tiles
+    tiled(_dev(x[:, :32, :48]))                                      # N = 2 < tile_batch: one call on both tiles
     assert len(seen) == 1 and np.array_equal(seen[0][0], R.split(x[:, :32, :48], 32, 16)) and seen[0][0].shape[0] == 2
 
 

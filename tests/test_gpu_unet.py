@@ -11,9 +11,10 @@ import blind_image_denoising_amd as bf
 from blind_image_denoising_amd import unet_laplacian as UL
 from oracle import bfcnn_oracle as O
 from oracle import unet_oracle as U
-from helpers import dev, host, assert_close
+from helpers import host, assert_close
+from guarded import dev as dev_raw, dev_f32 as dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 
 def _rng(seed):
@@ -326,7 +327,7 @@ def test_first_conv_normalise_and_virtual_padding(u8):
     w = r.normal(size=(5, 5, 3, 32)) * 0.2
     padded = np.zeros((2, 16, 32, 3)); padded[:, :13, :21] = img
     ref = U.act(O.conv2d_same(O.layer_normalize(padded, 0.0, 255.0), w), "leaky_relu_01")
-    x = torch.from_numpy(img).cuda() if u8 else dev(img)
+    x = dev_raw(img) if u8 else dev(img)
     got = UL.first_conv(x, dev(w), 16, 32, "leaky_relu_01", True, 0.0, 255.0)
     assert_close(host(got), ref, what="first conv")
 
@@ -343,7 +344,7 @@ def test_first_conv_split_f16(u8, shape, padded_hw, ks):
     H, W = padded_hw
     padded = np.zeros((shape[0], H, W, 3)); padded[:, :shape[1], :shape[2]] = img
     pre = O.conv2d_same(O.layer_normalize(padded, 0.0, 255.0), w)
-    x = torch.from_numpy(img).cuda() if u8 else dev(img)
+    x = dev_raw(img) if u8 else dev(img)
     for act in ("leaky_relu_01", "linear", "relu", "gelu"):
         got = UL.first_conv(x, dev(w), H, W, act, True, 0.0, 255.0, arith=1)
         assert_close(host(got), U.act(pre, act), what=f"first conv f16x3 {act}")
@@ -572,7 +573,7 @@ def test_full_size_config_512_batch_properties_and_256_oracle():
     assert np.array_equal(full[2:3], mod(big[2:3]))
     # the batch of the config itself: 32 x 512 x 512 (the three images above tiled; device tensors in, device tensor out)
     import torch
-    b32 = torch.from_numpy(np.concatenate([big] * 11)[:32]).cuda()
+    b32 = dev_raw(np.concatenate([big] * 11)[:32])
     out32 = mod(b32)
     assert out32.shape == b32.shape and out32.dtype == torch.uint8 and torch.equal(out32, mod(b32))
     got = out32.cpu().numpy()
@@ -608,7 +609,7 @@ def test_conv2d_transpose_matches_oracle(k, s, shape):
     x = rng.standard_normal((B, H, W, cin)).astype(np.float32)
     w = (rng.standard_normal((k, k, cout, cin)) * 0.2).astype(np.float32)
     for act in ("linear", "leaky_relu_01"):
-        got = UL.conv2d_transpose(torch.from_numpy(x).cuda(), torch.from_numpy(w).cuda(), s, act).cpu().numpy()
+        got = UL.conv2d_transpose(dev_raw(x), dev_raw(w), s, act).cpu().numpy()
         ref = U.act(U.conv2d_transpose_same(x.astype(np.float64), w.astype(np.float64), s), act)
         assert got.shape == ref.shape
         assert np.abs(got - ref).max() <= 2e-5 * max(1.0, np.abs(ref).max())

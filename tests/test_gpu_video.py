@@ -11,18 +11,15 @@ from blind_image_denoising_amd import _native as N
 from oracle import bfcnn_oracle as O
 import burst_reference as R
 import video_reference as V
+from guarded import dev as _dev, guard_bands
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guard_bands")]
 
 # (H, W, C) at B = 2.  5 x 7 is below a tile, 16 x 16 is one tile, 37 x 45 has cut edge tiles and, by its channels, rows of the
 # state that start on no dword (C = 1, 3), on a dword for the halfwords alone (C = 2) and for the bytes too (C = 4); 64 x 96 has
 # six tiles in a row (24 tiles in all: three to an XCD's share of the grid)
 SHAPES = [(5, 7, 1), (5, 7, 3), (16, 16, 3), (37, 45, 1), (37, 45, 2), (37, 45, 3), (37, 45, 4), (64, 96, 3)]
 _ids = {"ids": lambda c: "-".join(map(str, c))}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _same(got, ref):
