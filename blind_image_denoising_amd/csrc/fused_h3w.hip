@@ -30,6 +30,11 @@
 //     accumulator starts as the residual (s2 I) x [x_hi | x_lo] on top of the folded shift); A2 consumes x1 row s-8 ->
 //     second intermediate row s-9; B2 consumes it in step s+1 and completes AND stores output row s-11 in step s (staged: the
 //     storer stores it in s+1).  ONE barrier per step, nrows + 12 steps per band;
+//   * inside a step (H3W_EPI_ORDER 2) a wave takes its three groups one after the other, and each group accumulator by accumulator: the
+//     five MFMAs of the row it COMPLETES first (a2), then the five of the row above (a1), then [the residual and] the five of the row it
+//     starts (c0).  The completed row's epilogue -- 10 or 14 one-instruction micro-ops, the last two its LDS writes or global stores -- rides
+//     two by two behind MFMA 7, 8, ... of the SAME group, so the last MFMA of a step is followed by the barrier alone and the group-0
+//     shadows are used.  Every accumulator still receives its own five (six) MFMAs in the order it always did: same bits;
 //   * rows and columns outside the image are forced to zero in every ring (they are the NEXT convolution's zero padding,
 //     not values computed from padded input);
 //   * the FIRST launch of a forward on uint8 images (FusedH3WArgs::base_u8, template parameter BASE) has no loader: it computes
@@ -92,6 +97,29 @@
 #define H3W_DIRECT_STORE 1
 #endif
 
+// order of a group's MFMAs and place of the epilogues inside a role's step (every accumulator receives its own MFMAs in the same order under
+// every value, so the results are the same bits):
+// 0 = taps interleaved (a2, a1, c0 per tap); a group's epilogue rides behind MFMA 2, 3, ... of the NEXT group, the last group's runs behind the
+//     step's last MFMA, in front of the barrier, in nobody's shadow;
+// 1 = the LAST group of a step multiplies accumulator by accumulator (a2 x 5, a1 x 5, [residual,] c0 x 5): the row it completes is final after
+//     its fifth MFMA and its own epilogue rides behind MFMA 7, 8, ... of the same group, the previous group's behind MFMA 0 .. 6;
+// 2 = every group in that order with its own epilogue behind its own MFMA 7, 8, ...: no hand-over between groups, group 0's shadows are used
+// Same-box A/B (profiles/r08_pair_schedule_ab.txt): 2 +4.2 % images/s, 1 +2.1 %.
+#ifndef H3W_EPI_ORDER
+#define H3W_EPI_ORDER 2
+#endif
+// operands of step s+1 that are final a step earlier are read in step s, in front of the barrier:
+// 0 = every operand is read behind the barrier that starts its step;
+// 1 = the B roles read the residual operand of group 0 of step s+1 during the last group of step s (B1: x0 ring row s, which A1 consumes in
+//     step s; B2: the x1 row B1 completed in step s-1) and carry it across the barrier, so their first MFMA waits for no LDS read;
+// 2 = 1 + every role reads its group-1 fragment behind its first MFMA instead of in front of it: the twelve waves' group-0 reads are served first
+// Neither paid: alone inside the parent's spread, with H3W_EPI_ORDER 2 (where the residual is the eleventh MFMA of a group) -0.4 / -0.6 %.
+// A1's own fragment cannot be read early: its x0 row is final only at the barrier in front of its step, in the loader launch too (H3WMem<1>::end).
+#ifndef H3W_PREFETCH
+#define H3W_PREFETCH 0
+#endif
+static_assert(H3W_EPI_ORDER >= 0 && H3W_EPI_ORDER <= 2 && H3W_PREFETCH >= 0 && H3W_PREFETCH <= 2, "schedule constants");
+
 struct H3WGeom {
     static constexpr int NG = 9, GW = 16 * NG;         // grid: nine 16-column groups
     static constexpr int G = 3;                        // groups per matrix wave
@@ -124,7 +152,12 @@ struct H3WGeom {
     static_assert(3 * X0_PLANE + NRX0 * PITCH < 65536, "fragment offsets fit the 16-bit ds offset");
 };
 
-struct H3WTile : BandUnit {      // a band of one strip (h3_bands.h) + the strip's columns
+// H3W_EPI_ORDER: the groups of a wave that multiply accumulator by accumulator, and the MFMA of such a group behind which the first micro-ops
+// of its own epilogue ride.  The accumulator they read was finished by MFMA 4: three MFMAs lie in between, one more than the rule above H3VEpi asks for
+constexpr bool h3w_grouped(const int g) { return H3W_EPI_ORDER == 2 || (H3W_EPI_ORDER == 1 && g == H3WGeom::G - 1); }
+constexpr int H3W_OWN_SLOT = 7;
+
+struct H3WTile : BandUnit {    // a band of one strip (h3_bands.h) + the strip's columns
     int X0, X1;                  // output columns [X0, X1)
     int G0;                      // image column of grid column 0
     int D0, D1;                  // x0 columns fetched: [D0, D1), inside the grid and the image
@@ -201,12 +234,15 @@ struct H3WRoleA {
         return e;
     }
 
-    // the 15 MFMAs of group g; micro-ops of the previous group's epilogue after MFMA 2, 3, ...
-    template <int J, class Epi>
-    __device__ __forceinline__ void mfmas(const int g, const int a1, const int a2, const H3VFrag& cur, f32x4& c0, Epi* epi)
+    // MFMAs [J, JEND) of the 15 of group g.  !GROUPED: the taps interleaved, micro-ops of the previous group's epilogue (prev) after MFMA 2,
+    // 3, ...  GROUPED: a2 x 5, a1 x 5, c0 x 5; prev's micro-ops after MFMA 0 .. 6, and after MFMA H3W_OWN_SLOT (three MFMAs behind the one
+    // that finished acc[g][a2]), ... those of the group's own epilogue, which is built there into *own
+    template <int J, int JEND, bool GROUPED, class Epi>
+    __device__ __forceinline__ void mfmas(const int g, const int a1, const int a2, const H3VFrag& cur, f32x4& c0, Epi* prev, Epi* own,
+                                          const int mslot, const bool rowok)
     {
-        if constexpr (J < 15) {
-            constexpr int k = J / 3, which = J % 3;
+        if constexpr (J < JEND) {
+            constexpr int k = GROUPED ? J % 5 : J / 3, which = GROUPED ? J / 5 : J % 3;
             if (!(H3V_ABLATE & 8) && !(skip_last && g == Gm::G - 1)) {
                 if constexpr (which == 0) acc[g][a2] = h3v_mfma(cur, w, 2, k, acc[g][a2]);
                 else if constexpr (which == 1) acc[g][a1] = h3v_mfma(cur, w, 1, k, acc[g][a1]);
@@ -215,39 +251,66 @@ struct H3WRoleA {
                 acc[g][a2][0] += (float)cur.ph[0] + (float)cur.pl[1] + (float)cur.s[2];
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (J >= 2) {
-                if (epi) epi->template pair<J - 2>();
+            if constexpr (!GROUPED) {
+                if constexpr (J >= 2) {
+                    if (prev) prev->template pair<J - 2>();
+                }
+            } else if constexpr (J < H3W_OWN_SLOT) {
+                if (prev) prev->template pair<J>();
+            } else {
+                if constexpr (J == H3W_OWN_SLOT) *own = epilogue(g, mslot, acc[g][a2], rowok);
+                own->template pair<J - H3W_OWN_SLOT>();
             }
-            mfmas<J + 1>(g, a1, a2, cur, c0, epi);
+            mfmas<J + 1, JEND, GROUPED>(g, a1, a2, cur, c0, prev, own, mslot, rowok);
         }
+    }
+
+    // group g of step s: the loop body of step() as a template, so that the order of a group is a constant of its instantiation
+    template <int PH, int g, class Hook>
+    __device__ __forceinline__ void group(H3VFrag& cur, const int islot_bytes, const bool rowok, Hook& hook)
+    {
+        constexpr int a0 = PH % 3, a1 = (PH + 2) % 3, a2 = (PH + 1) % 3;      // accumulators of intermediate rows s, s-1, s-2
+        constexpr int mslot = PH % Gm::NRM;
+        constexpr bool grouped = h3w_grouped(g);
+        constexpr bool late_nx = H3W_PREFETCH == 2 && g == 0;        // the group-1 fragment is read behind the step's first MFMA
+        using Epi = H3VEpi<true>;
+        H3VFrag nx;
+        Epi own;
+        if constexpr (g + 1 < Gm::G && !late_nx) nx = load(islot_bytes, g + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 c0 = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (g > 0 && H3W_EPI_ORDER != 2) {
+            Epi e = epilogue(g - 1, mslot, acc[g - 1][a2], rowok);
+            mfmas<0, 15, grouped>(g, a1, a2, cur, c0, &e, &own, mslot, rowok);
+        } else {
+            mfmas<0, 1, grouped>(g, a1, a2, cur, c0, (Epi*)nullptr, &own, mslot, rowok);
+            if constexpr (late_nx) {
+                nx = load(islot_bytes, 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            mfmas<1, 15, grouped>(g, a1, a2, cur, c0, (Epi*)nullptr, &own, mslot, rowok);
+        }
+        if constexpr (g == 0) {
+            hook.after_first_group();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        acc[g][a0] = c0;
+        if constexpr (g + 1 < Gm::G) cur = nx;
     }
 
     // step s (s % UNROLL == PH): consumes the ring row at byte offset islot_bytes, completes the intermediate row of slot PH % 2
     template <int PH, class Hook>
     __device__ __forceinline__ void step(const int islot_bytes, const bool rowok, Hook& hook)
     {
-        constexpr int a0 = PH % 3, a1 = (PH + 2) % 3, a2 = (PH + 1) % 3;      // accumulators of intermediate rows s, s-1, s-2
-        constexpr int mslot = PH % Gm::NRM;
+        static_assert(Gm::G == 3, "three groups per wave");
         H3VFrag cur = load(islot_bytes, 0);
-#pragma unroll
-        for (int g = 0; g < Gm::G; ++g) {
-            H3VFrag nx;
-            if (g + 1 < Gm::G) nx = load(islot_bytes, g + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            f32x4 c0 = {0.f, 0.f, 0.f, 0.f};
-            if (g > 0) {
-                H3VEpi<true> e = epilogue(g - 1, mslot, acc[g - 1][a2], rowok);
-                mfmas<0>(g, a1, a2, cur, c0, &e);
-            } else {
-                mfmas<0>(g, a1, a2, cur, c0, (H3VEpi<true>*)nullptr);
-                hook.after_first_group();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            acc[g][a0] = c0;
-            if (g + 1 < Gm::G) cur = nx;
+        group<PH, 0>(cur, islot_bytes, rowok, hook);
+        group<PH, 1>(cur, islot_bytes, rowok, hook);
+        group<PH, 2>(cur, islot_bytes, rowok, hook);
+        if constexpr (!h3w_grouped(Gm::G - 1)) {
+            H3VEpi<true> e = epilogue(Gm::G - 1, PH % Gm::NRM, bf_acc_ready(acc[Gm::G - 1][(PH + 1) % 3]), rowok);
+            e.all();
         }
-        H3VEpi<true> e = epilogue(Gm::G - 1, mslot, bf_acc_ready(acc[Gm::G - 1][a2]), rowok);
-        e.all();
     }
 };
 
@@ -255,8 +318,9 @@ struct H3WRoleA {
 // role B: a block's second convolution + folded BN + residual.  B1 writes the x1 ring, B2 the staging rows.
 // ---------------------------------------------------------------------------------------------------------------------
 // The epilogue of a role that stores its output row itself (B2 under H3W_DIRECT_STORE): micro-ops 0 .. 7 of H3VEpi<false>, then the lane's
-// two 8-byte records (hi, lo) go to global memory where micro-ops 8 and 9 wrote them to LDS -- behind the sixth MFMA of the next group,
-// the last group's at the end of the step.  mask: the lanes that store -- the row is one of the band's (else 0) and the lane's column one
+// two 8-byte records (hi, lo) go to global memory where micro-ops 8 and 9 wrote them to LDS -- as the fifth pair of the epilogue, wherever
+// H3W_EPI_ORDER places it (2: behind MFMA 11 of the group's own sixteen; 0: behind the sixth MFMA of the next group, the last group's at
+// the end of the step).  mask: the lanes that store -- the row is one of the band's (else 0) and the lane's column one
 // of the strip's; a wave-uniform lane mask, so the guard is one scalar instruction on the execution mask and no vector one.
 struct H3WEpiStore : H3VEpi<false> {
     char* image;
@@ -300,6 +364,7 @@ struct H3WRoleB {                                       // DIRECT: no LDS output
     f32x4 shs;                   // folded BN shift of the lane's four channels times s2 (the accumulators' scale)
     float lane_scale[Gm::G];
     bool skip_last = false;      // timing experiment (H3V_ABLATE & 256)
+    h8 xr_pre;                   // H3W_PREFETCH: the residual operand of group 0 of the next step, carried across the barrier
     // DIRECT only
     char* gout;                  // FusedH3WArgs::out
     char* image;                 // the unit's image in it
@@ -319,6 +384,7 @@ struct H3WRoleB {                                       // DIRECT: no LDS output
         go = 0;
         have = false;
         row_hi = row_lo = 0;
+        xr_pre = (h8){0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int g = 0; g < Gm::G; ++g) okm[g] = 0;
 #pragma unroll
@@ -394,17 +460,21 @@ struct H3WRoleB {                                       // DIRECT: no LDS output
         return e;
     }
 
-    // the 1 + 15 MFMAs of group g; micro-ops of the previous group's epilogue after MFMA 2, 3, ...
-    template <int J, class Epi>
-    __device__ __forceinline__ void mfmas(const int g, const int a1, const int a2, const H3VFrag& cur, const h8 xr, f32x4& c0, Epi* epi)
+    // MFMAs [J, JEND) of the 1 + 15 of group g.  !GROUPED: the residual, then the taps interleaved; micro-ops of the previous group's epilogue
+    // (prev) after MFMA 2, 3, ...  GROUPED: a2 x 5, a1 x 5, the residual, c0 x 5; prev's micro-ops after MFMA 0 .. 6, those of the group's own
+    // epilogue, built there into *own, after MFMA H3W_OWN_SLOT, ... (as H3WRoleA::mfmas)
+    template <int J, int JEND, bool GROUPED, class Epi>
+    __device__ __forceinline__ void mfmas(const int g, const int a1, const int a2, const H3VFrag& cur, const h8 xr, f32x4& c0, Epi* prev, Epi* own,
+                                          const int oslot_bytes, const bool rowok)
     {
-        if constexpr (J < 16) {
+        if constexpr (J < JEND) {
+            constexpr int RES = GROUPED ? 10 : 0, T = J - (J > RES ? 1 : 0);      // the residual's place; the tap MFMA's index among the 15
             if (!(H3V_ABLATE & 4) && !(skip_last && g == Gm::G - 1)) {
-                if constexpr (J == 0) {
+                if constexpr (J == RES) {
                     // residual: (s2 * I) x [x_hi | x_lo], exact, on top of the folded BN shift (times s2) as the C operand
                     c0 = MFMA_H(w[12], xr, shs);
                 } else {
-                    constexpr int k = (J - 1) / 3, which = (J - 1) % 3;
+                    constexpr int k = GROUPED ? T % 5 : T / 3, which = GROUPED ? T / 5 : T % 3;
                     if constexpr (which == 0) acc[g][a2] = h3v_mfma(cur, w, 2, k, acc[g][a2]);
                     else if constexpr (which == 1) acc[g][a1] = h3v_mfma(cur, w, 1, k, acc[g][a1]);
                     else c0 = h3v_mfma(cur, w, 0, k, c0);
@@ -413,48 +483,84 @@ struct H3WRoleB {                                       // DIRECT: no LDS output
                 acc[g][a2][0] += (float)cur.ph[0] + (float)cur.pl[1] + (float)cur.s[2] + (float)xr[3];
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (J >= 2) {
-                if (epi) epi->template pair<J - 2>();
+            if constexpr (!GROUPED) {
+                if constexpr (J >= 2) {
+                    if (prev) prev->template pair<J - 2>();
+                }
+            } else if constexpr (J < H3W_OWN_SLOT) {
+                if (prev) prev->template pair<J>();
+            } else {
+                if constexpr (J == H3W_OWN_SLOT) *own = epilogue(g, oslot_bytes, acc[g][a2], rowok);
+                own->template pair<J - H3W_OWN_SLOT>();
             }
-            mfmas<J + 1>(g, a1, a2, cur, xr, c0, epi);
+            mfmas<J + 1, JEND, GROUPED>(g, a1, a2, cur, xr, c0, prev, own, oslot_bytes, rowok);
+        }
+    }
+
+    // H3W_PREFETCH: the residual operand of group 0 of the NEXT step (byte offset next_xslot_bytes of its ring: a row that is final in this
+    // step) -- read in the last group of a step, and in every step the role has no row in, so that each of its steps finds it in registers
+    __device__ __forceinline__ void prefetch(const int next_xslot_bytes)
+    {
+        if (H3W_PREFETCH) xr_pre = load_res(next_xslot_bytes, 0);
+    }
+
+    // group g of step s (as H3WRoleA::group)
+    template <int PH, int g, class Hook>
+    __device__ __forceinline__ void group(H3VFrag& cur, h8& xr, const int xslot_bytes, const int next_xslot_bytes, const int oslot_bytes,
+                                          const bool rowok, Hook& hook)
+    {
+        constexpr int mslot = (PH + 1) % Gm::NRM;                              // (s - 1) mod 2
+        constexpr int a0 = PH % 3, a1 = (PH + 2) % 3, a2 = (PH + 1) % 3;
+        constexpr bool grouped = h3w_grouped(g);
+        constexpr bool late_nx = H3W_PREFETCH == 2 && g == 0;        // the group-1 operands are read behind the step's first MFMA
+        H3VFrag nx;
+        h8 xn;
+        Epi own;
+        if constexpr (g + 1 < Gm::G && !late_nx) {
+            nx = load(mslot, g + 1);
+            xn = load_res(xslot_bytes, g + 1);
+        }
+        if constexpr (g + 1 == Gm::G) prefetch(next_xslot_bytes);
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 c0;
+        if constexpr (g > 0 && H3W_EPI_ORDER != 2) {
+            Epi e = epilogue(g - 1, oslot_bytes, acc[g - 1][a2], rowok);
+            mfmas<0, 16, grouped>(g, a1, a2, cur, xr, c0, &e, &own, oslot_bytes, rowok);
+        } else {
+            mfmas<0, 1, grouped>(g, a1, a2, cur, xr, c0, (Epi*)nullptr, &own, oslot_bytes, rowok);
+            if constexpr (late_nx) {
+                nx = load(mslot, 1);
+                xn = load_res(xslot_bytes, 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            mfmas<1, 16, grouped>(g, a1, a2, cur, xr, c0, (Epi*)nullptr, &own, oslot_bytes, rowok);
+        }
+        if constexpr (g == 0) {
+            hook.after_first_group();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        acc[g][a0] = c0;
+        if constexpr (g + 1 < Gm::G) {
+            cur = nx;
+            xr = xn;
         }
     }
 
     // step s (s % UNROLL == PH): consumes the intermediate row completed in step s-1, starts an output row with the residual at
-    // byte offset xslot_bytes of its ring, completes the output row of byte offset oslot_bytes
+    // byte offset xslot_bytes of its ring (next_xslot_bytes: the one of step s+1), completes the output row of byte offset oslot_bytes
     template <int PH, class Hook>
-    __device__ __forceinline__ void step(const int xslot_bytes, const int oslot_bytes, const bool rowok, Hook& hook)
+    __device__ __forceinline__ void step(const int xslot_bytes, const int next_xslot_bytes, const int oslot_bytes, const bool rowok, Hook& hook)
     {
-        constexpr int mslot = (PH + 1) % Gm::NRM;                              // (s - 1) mod 2
-        constexpr int a0 = PH % 3, a1 = (PH + 2) % 3, a2 = (PH + 1) % 3;
-        H3VFrag cur = load(mslot, 0);
-        h8 xr = load_res(xslot_bytes, 0);
-#pragma unroll
-        for (int g = 0; g < Gm::G; ++g) {
-            H3VFrag nx;
-            h8 xn;
-            if (g + 1 < Gm::G) {
-                nx = load(mslot, g + 1);
-                xn = load_res(xslot_bytes, g + 1);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            f32x4 c0;
-            if (g > 0) {
-                Epi e = epilogue(g - 1, oslot_bytes, acc[g - 1][a2], rowok);
-                mfmas<0>(g, a1, a2, cur, xr, c0, &e);
-            } else {
-                mfmas<0>(g, a1, a2, cur, xr, c0, (Epi*)nullptr);
-                hook.after_first_group();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            acc[g][a0] = c0;
-            if (g + 1 < Gm::G) {
-                cur = nx;
-                xr = xn;
-            }
+        static_assert(Gm::G == 3, "three groups per wave");
+        H3VFrag cur = load((PH + 1) % Gm::NRM, 0);
+        h8 xr = H3W_PREFETCH ? xr_pre : load_res(xslot_bytes, 0);
+        group<PH, 0>(cur, xr, xslot_bytes, next_xslot_bytes, oslot_bytes, rowok, hook);
+        group<PH, 1>(cur, xr, xslot_bytes, next_xslot_bytes, oslot_bytes, rowok, hook);
+        group<PH, 2>(cur, xr, xslot_bytes, next_xslot_bytes, oslot_bytes, rowok, hook);
+        if constexpr (!h3w_grouped(Gm::G - 1)) {
+            Epi e = epilogue(Gm::G - 1, oslot_bytes, bf_acc_ready(acc[Gm::G - 1][(PH + 1) % 3]), rowok);
+            e.all();
         }
-        Epi e = epilogue(Gm::G - 1, oslot_bytes, bf_acc_ready(acc[Gm::G - 1][a2]), rowok);
-        e.all();
     }
 };
 
@@ -882,8 +988,8 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
 
 #define H3W_ROW_IN_IMAGE(k) ((t.y(k) >= 0) & (t.y(k) < a.H))
 // one band of one strip: R = the matrix role object, M = its memory hook, P = its share of the producer, ACTIVE(s) = the role has a row in step s,
-// STEP(PH) = the role's step call.  Every role runs the same number of barriers.
-#define H3W_BAND(R, M, P, ACTIVE, STEP)                                                                         \
+// STEP(PH) = the role's step call, IDLE(PH) = what it does in a step it has no row in.  Every role runs the same number of barriers.
+#define H3W_BAND(R, M, P, ACTIVE, STEP, IDLE)                                                                        \
     for (int ti = blockIdx.x; ti < a.ntiles; ti += gridDim.x) {                                               \
         const H3WTile t = h3w_tile(a, ti);                                                                    \
         R.set_tile(t, a.W, gc0);                                                                              \
@@ -899,19 +1005,19 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         const int nsteps = t.nrows + Gm::LEAD;                                                                \
         int slot5 = 0;                                       /* s mod 5 */                                    \
         for (int s0 = 0; s0 < nsteps; s0 += Gm::UNROLL) {                                                     \
-            H3W_ONE(0, M, P, ACTIVE, STEP); H3W_ONE(1, M, P, ACTIVE, STEP); H3W_ONE(2, M, P, ACTIVE, STEP);   \
-            H3W_ONE(3, M, P, ACTIVE, STEP); H3W_ONE(4, M, P, ACTIVE, STEP); H3W_ONE(5, M, P, ACTIVE, STEP);   \
+            H3W_ONE(0, M, P, ACTIVE, STEP, IDLE); H3W_ONE(1, M, P, ACTIVE, STEP, IDLE); H3W_ONE(2, M, P, ACTIVE, STEP, IDLE); \
+            H3W_ONE(3, M, P, ACTIVE, STEP, IDLE); H3W_ONE(4, M, P, ACTIVE, STEP, IDLE); H3W_ONE(5, M, P, ACTIVE, STEP, IDLE); \
         }                                                                                                     \
         M.finish();                                                                                           \
         h3v_barrier();                                                                                        \
     }
-#define H3W_ONE(PH, M, P, ACTIVE, STEP)                                                                         \
+#define H3W_ONE(PH, M, P, ACTIVE, STEP, IDLE)                                                                       \
     do {                                                                                                      \
         const int s = s0 + PH;                                                                                \
         P.begin(t, s);                                                                                        \
         M.begin(t, s, PH);                                                                                    \
         if (ACTIVE(s)) { STEP(PH); }                                                                          \
-        else M.after_first_group();                                                                           \
+        else { M.after_first_group(); IDLE(PH); }                                                             \
         slot5 = h3v_wrap(slot5 + 1, Gm::NRX0);                                                                \
         H3V_STAMP(0);                                                                                         \
         M.end();                                                                                              \
@@ -932,9 +1038,11 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));               // weight / scale loads
 #define H3W_ACTIVE(s) ((s) < t.nrows + 8)
 #define H3W_STEP(PH) R.template step<PH>(slot5 * Gm::PITCH, (s >= 2) & H3W_ROW_IN_IMAGE(s - 5), M)
-        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP)
+#define H3W_IDLE(PH) do { } while (0)
+        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP, H3W_IDLE)
 #undef H3W_ACTIVE
 #undef H3W_STEP
+#undef H3W_IDLE
     } else if (role == 1) {
         // ---- B1: conv2a + residual x0 (ring row s-1) -> x1 ring
         __builtin_amdgcn_s_setprio(H3W_PRIO_B1);
@@ -946,10 +1054,13 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         H3WProducer<BASE ? h3w_base_groups(1) : 0, BASE && h3w_base_groups(1) && h3w_base_fetches(1)> P(a, h3w_lds, h3w_base_first_group(1, rw), rw);
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));
 #define H3W_ACTIVE(s) (((s) >= 3) & ((s) < t.nrows + 9))
-#define H3W_STEP(PH) R.template step<PH>(h3v_wrap(slot5 + Gm::NRX0 - 1, Gm::NRX0) * Gm::PITCH, (PH % Gm::NRX1) * Gm::PITCH, H3W_ROW_IN_IMAGE(s - 7), M)
-        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP)
+        // the residual of step s is x0 ring row s-1; the one of step s+1, row s (slot5: the row A1 consumes in this step), is final already
+#define H3W_STEP(PH) R.template step<PH>(h3v_wrap(slot5 + Gm::NRX0 - 1, Gm::NRX0) * Gm::PITCH, slot5 * Gm::PITCH, (PH % Gm::NRX1) * Gm::PITCH, H3W_ROW_IN_IMAGE(s - 7), M)
+#define H3W_IDLE(PH) R.prefetch(slot5 * Gm::PITCH)
+        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP, H3W_IDLE)
 #undef H3W_ACTIVE
 #undef H3W_STEP
+#undef H3W_IDLE
     } else if (role == 2) {
         // ---- A2: conv1b on the x1 ring -> second intermediate ring
         __builtin_amdgcn_s_setprio(H3W_PRIO_A2);
@@ -962,9 +1073,11 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));
 #define H3W_ACTIVE(s) (((s) >= 6) & ((s) < t.nrows + 10))
 #define H3W_STEP(PH) R.template step<PH>(((PH + 2) % Gm::NRX1) * Gm::PITCH, H3W_ROW_IN_IMAGE(s - 9), M)
-        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP)
+#define H3W_IDLE(PH) do { } while (0)
+        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP, H3W_IDLE)
 #undef H3W_ACTIVE
 #undef H3W_STEP
+#undef H3W_IDLE
     } else {
         // ---- B2: conv2b + residual x1 -> staging rows, or (DIRECT) global memory: output row s - 11 is complete in step s
         __builtin_amdgcn_s_setprio(H3W_PRIO_B2);
@@ -976,10 +1089,13 @@ __global__ __launch_bounds__(H3WGeom::NT, 3) void fused_block2_h3w_kernel(FusedH
         H3WProducer<BASE ? h3w_base_groups(3) : 0, BASE && h3w_base_groups(3) && h3w_base_fetches(3)> P(a, h3w_lds, h3w_base_first_group(3, rw), rw);
         __builtin_amdgcn_s_waitcnt(h3_vmcnt(0));
 #define H3W_ACTIVE(s) (((s) >= 9) & ((s) < t.nrows + 11))
-#define H3W_STEP(PH) R.set_row(t, a.W, s - (Gm::LEAD - 1)); R.template step<PH>(((PH + 1) % Gm::NRX1) * Gm::PITCH, (PH % Gm::NRO) * Gm::OUT_SLOT, true, M)
-        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP)
+        // the residual of step s is the x1 row B1 completed in step s-2; the one of step s+1 was completed in step s-1 (the row A2 consumes now)
+#define H3W_STEP(PH) R.set_row(t, a.W, s - (Gm::LEAD - 1)); R.template step<PH>(((PH + 1) % Gm::NRX1) * Gm::PITCH, ((PH + 2) % Gm::NRX1) * Gm::PITCH, (PH % Gm::NRO) * Gm::OUT_SLOT, true, M)
+#define H3W_IDLE(PH) R.prefetch(((PH + 2) % Gm::NRX1) * Gm::PITCH)
+        H3W_BAND(R, M, P, H3W_ACTIVE, H3W_STEP, H3W_IDLE)
 #undef H3W_ACTIVE
 #undef H3W_STEP
+#undef H3W_IDLE
     }
 #undef H3W_BAND
 #undef H3W_ONE

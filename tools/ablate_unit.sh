@@ -2,6 +2,8 @@
 # Timing-only variants of ONE translation unit: recompiles <unit>.hip with -D<MACRO>=<v> and links it with the current
 # objects of the other units (blind_image_denoising_amd/lib/obj, i.e. run csrc/build.sh first).
 #   tools/ablate_unit.sh fused_h3v H3V_ABLATE 1 2 3 12 32   ->  lib/variants/libbfcnn_hip_H3V_ABLATE<v>.so
+# A second constant: ABLATE_FLAGS (extra compiler flags) and ABLATE_TAG (a suffix of the file names), e.g.
+#   ABLATE_FLAGS=-DH3W_PREFETCH=1 ABLATE_TAG=_P1 tools/ablate_unit.sh fused_h3w H3W_EPI_ORDER 1 2   ->  ...H3W_EPI_ORDER<v>_P1.so
 set -euo pipefail
 cd "$(dirname "$0")/.."
 unit="$1"; macro="$2"; shift 2
@@ -17,9 +19,9 @@ pids=()
 for v in "$@"; do
     (
         /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-pass-failed \
-            "-D${macro}=${v}" -c "$src/$unit.hip" -o "$out/${unit}_${macro}${v}.o"
-        /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC "${others[@]}" "$out/${unit}_${macro}${v}.o" -ldl \
-            -o "$out/libbfcnn_hip_${macro}${v}.so"
+            "-D${macro}=${v}" ${ABLATE_FLAGS:-} -c "$src/$unit.hip" -o "$out/${unit}_${macro}${v}${ABLATE_TAG:-}.o"
+        /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC "${others[@]}" "$out/${unit}_${macro}${v}${ABLATE_TAG:-}.o" -ldl \
+            -o "$out/libbfcnn_hip_${macro}${v}${ABLATE_TAG:-}.so"
     ) &
     pids+=($!)
 done
